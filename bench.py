@@ -28,6 +28,18 @@ from tests/host_transport.py, and the output says so).
 Prints ONE JSON line (rank 0): metric / value in Mcells/s (raster cells through the whole step, all ranks), `roofline` for
 the dominant kernel (HIP-event time on the launch stream; HBM traffic from profiles/pmc_traffic.json when -- and only when --
 it was collected on the very build that is loaded), `cpu_baseline` = the CPU oracle timed on this box.
+
+A plain run only sets up, warms up, times the K steps and prints that line.  Everything else it can measure or check runs
+only with `--full`: the CPU baseline, the streaming-copy yardstick of the roofline (`roofline.measured_copy_gbs`), the
+informational per-kernel / nodata / sustained figures and the other two workloads (config.*), the strong-scaling workloads
+of an N > 1 run, the shard-boundary checks (`halo_check`), the exact host counts of `zonal32k` and its API / rehearsal
+figures.
+
+`--dump-outputs DIR`: after the timed steps, the planes the last step wrote, as DIR/<name>.npy (float32; float64 for the
+zonal tables of the zones that hold cells), each rank's own rows (`_rank<r>` suffix when N > 1).  Hillshade and slope have
+no value on the raster's outermost row and column (NaN, as in the reference): that frame is left out.  A plane larger than
+16 MB is sampled by whole rows: its first and last two rows and a fixed, seeded choice of the others, ascending.  The inputs
+are seeded too, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import contextlib
@@ -57,6 +69,36 @@ SYM_FOCAL5 = "focal_mean_direct_kernel<5, 5, 4, 0u>"
 SYM_HILL = "terrain_strip_kernel<8, float, 4>"
 SYM_S64 = "raster_pass_kernel<9, 5, 5, 4, true, 4685252u>"
 SYM_ZONAL = "zonal_kernel<float, true, true, 1024, 2>"     # (1000 zones: 2 table slots per lane)
+DUMP_BYTES_PER_PLANE = 16 << 20   # --dump-outputs: at most three planes per workload, 48 MB in all
+
+
+def dump_rows(lo, hi, width, seed=0):
+    """Row indices --dump-outputs writes of rows [lo, hi) of a float32 plane `width` cells wide: all of them if they fit in
+    DUMP_BYTES_PER_PLANE, else the first and last two and a seeded choice of the others, ascending."""
+    n = max(4, DUMP_BYTES_PER_PLANE // (4 * max(width, 1)))
+    if hi - lo <= n:
+        return np.arange(lo, hi)
+    inner = np.random.default_rng(seed).choice(np.arange(lo + 2, hi - 2), n - 4, replace=False)
+    return np.sort(np.concatenate([[lo, lo + 1, hi - 2, hi - 1], inner]))
+
+
+def dump_outputs(ctx, planes=(), tables=()):
+    """--dump-outputs.  planes = [(name, DeviceArray, frame)]: 2-D float32 planes of this rank's rows whose outermost `frame`
+    rows and columns of the whole raster have no value by definition (hillshade, slope: NaN where the 3x3 stencil leaves the
+    raster, as in the reference), so only the cells inside that frame are written, rows sampled by dump_rows (a shard's
+    halo-backed edge rows are inside it).  tables = [(name, ndarray)]: written whole, as float64."""
+    directory = ctx.args.dump_outputs
+    os.makedirs(directory, exist_ok=True)
+    suffix = f"_rank{ctx.rank}" if ctx.world > 1 else ""
+    for name, dev, frame in planes:
+        rows, cols = dev.shape
+        top = frame if ctx.rank == 0 else 0
+        bot = frame if ctx.rank == ctx.world - 1 else 0
+        idx = dump_rows(top, rows - bot, cols - 2 * frame)
+        host = np.stack([dev.rows(int(r), int(r) + 1).get(ctx.stream)[0, frame:cols - frame] for r in idx]).astype(np.float32)
+        np.save(os.path.join(directory, name + suffix + ".npy"), host)
+    for name, arr in tables:
+        np.save(os.path.join(directory, name + suffix + ".npy"), np.asarray(arr, dtype=np.float64))
 
 
 @contextlib.contextmanager
@@ -484,7 +526,7 @@ def run_headline(ctx):
     # both shards in one unsharded block -- the block around the boundary is regenerated, uploaded and run through one
     # pass on this GPU.  Bit for bit: sharding may not change a single result.
     halo_check = None
-    if world > 1:
+    if world > 1 and args.full:
         mismatched = 0
         for side, has_nb in (("top", rank > 0), ("bottom", rank < world - 1)):
             if not has_nb:
@@ -504,8 +546,10 @@ def run_headline(ctx):
                 mismatched += int(np.count_nonzero(~((got == want) | (np.isnan(got) & np.isnan(want)))))
         total_bad = ctx.allsum(mismatched)
         halo_check = {"cells_differing_from_the_unsharded_pass_at_shard_boundaries": int(total_bad), "ok": bool(total_bad == 0)}
+    if args.dump_outputs:                # (before the --full figures below, which reuse out_hill as scratch)
+        dump_outputs(ctx, [("hillshade", out_hill, 1), ("focal_mean_5x5", out_focal, 0)])
 
-    copy_gbs = ctx.copy_bandwidth(dem_ptr, out_hill.ptr, rows * cols) if rank == 0 else None
+    copy_gbs = ctx.copy_bandwidth(dem_ptr, out_hill.ptr, rows * cols) if rank == 0 and args.full else None
     # (Rounds 1-2 also reported xrs_stream_mix_f32 -- one plane read, two written -- as "the ceiling of the step's own
     #  traffic mix"; the fused pass beat it (1.07x), so it was no ceiling: dropped.  The yardstick is the 1:1 streaming copy.)
 
@@ -748,8 +792,8 @@ def run_headline(ctx):
             "launch_ms": round(dom_ms, 4),
             "launch_ms_from": ("HIP events around every launch" if (args.unfused or args.per_step_events) else
                                "one HIP event pair around the K timed launches on the launch stream / K (gaps included)"),
-            "measured_copy_gbs": round(copy_gbs, 1),
-            "frac_of_measured_copy": round(achieved / copy_gbs, 4),
+            "measured_copy_gbs": None if copy_gbs is None else round(copy_gbs, 1),
+            "frac_of_measured_copy": None if copy_gbs is None else round(achieved / copy_gbs, 4),
             "algorithmic_bytes_per_cell": alg_bytes,
         },
     }
@@ -869,10 +913,12 @@ def run_s64(ctx, steps=None, warmup=None, brief=False):
     ctx.barrier()
     elapsed = ctx.allmax(time.perf_counter() - t0)
     dev_ms = ctx.elapsed_ms(e0, e1) / steps
+    if args.dump_outputs and not brief:
+        dump_outputs(ctx, [("hillshade", o_hill, 1), ("slope", o_slope, 1), ("focal_mean_5x5", o_focal, 0)])
 
     # sharded correctness: the rows next to every shard boundary equal one unsharded pass over the rows of both shards
     halo_check = None
-    if world > 1:
+    if world > 1 and args.full:
         bad = 0
         for side, has_nb in (("top", rank > 0), ("bottom", rank < world - 1)):
             if not has_nb:
@@ -907,7 +953,7 @@ def run_s64(ctx, steps=None, warmup=None, brief=False):
             n1, src = n1_reference(ctx, "s64")
             out["speedup_vs_n1"] = None if n1 is None else round(n1 / (elapsed / steps * 1e3), 3)
             out["speedup_vs_n1_from"] = src
-    if world == 1:
+    if world == 1 and args.full:
         # the north_star bar: >= 70 % of the MEASURED copy bandwidth at 65536^2, fused and as three calls
         copy_gbs = ctx.copy_bandwidth(dem_ptr, o_hill.ptr, rows * cols)
         t3 = ctx.timed(three_calls, reps=3)
@@ -1046,17 +1092,24 @@ def run_zonal32k(ctx, steps=None, warmup=None, brief=False):
     ctx.barrier()
     elapsed = ctx.allmax(time.perf_counter() - t0)
     dev_ms = ctx.elapsed_ms(e0, e1) / steps
-    # exact expected counts: zone ids are constant on 1024 x 1024 blocks; finite cells per (band row-block, column block)
+    if args.dump_outputs and not brief:
+        cnt = zc.get(stream)
+        present = cnt > 0                          # (the zones a zonal.stats caller gets rows for; an empty zone has no min / max)
+        dump_outputs(ctx, tables=[("zonal_count", cnt[present])] + [(n, t.get(stream)[present]) for n, t in (
+            ("zonal_sum", zs), ("zonal_sum_sq", zq), ("zonal_min", zmn), ("zonal_max", zmx))])
     got = zc.get(stream).astype(np.int64)
-    fin = np.isfinite(band).astype(np.int32)
-    want = np.zeros(nz, np.int64)
-    colblk = np.add.reduceat(fin, np.arange(0, cols, block), axis=1)           # (band_rows, cols/block) finite cells per row
-    for bi in range(total_rows // block):
-        rows_in_band = (np.arange(bi * block, (bi + 1) * block) % band_rows)
-        per_col = colblk[rows_in_band].sum(axis=0)
-        ids = (bi * 32 + np.arange(cols // block)) % nz
-        np.add.at(want, ids, per_col)
-    counts_ok = bool((got == want).all())
+    counts_ok = None
+    if args.full:
+        # exact expected counts: zone ids are constant on 1024 x 1024 blocks; finite cells per (band row-block, column block)
+        fin = np.isfinite(band).astype(np.int32)
+        want = np.zeros(nz, np.int64)
+        colblk = np.add.reduceat(fin, np.arange(0, cols, block), axis=1)           # (band_rows, cols/block) finite cells per row
+        for bi in range(total_rows // block):
+            rows_in_band = (np.arange(bi * block, (bi + 1) * block) % band_rows)
+            per_col = colblk[rows_in_band].sum(axis=0)
+            ids = (bi * 32 + np.arange(cols // block)) % nz
+            np.add.at(want, ids, per_col)
+        counts_ok = bool((got == want).all())
     cells_total = float(total_rows) * cols
     out = {
         "raster": f"{total_rows}x{cols} float32 values + int32 zones, {nz} zones in {block}x{block} blocks", "rows_this_rank": rows,
@@ -1127,7 +1180,7 @@ def run_zonal32k(ctx, steps=None, warmup=None, brief=False):
             n1, src = n1_reference(ctx, "zonal32k")
             out["speedup_vs_n1"] = None if n1 is None else round(n1 / (elapsed / steps * 1e3), 3)
             out["speedup_vs_n1_from"] = src
-    if not counts_ok:
+    if counts_ok is False:
         out["count_mismatches"] = int(np.count_nonzero(got != want))
     del vals, zones
     return out
@@ -1303,7 +1356,15 @@ def main():
     ap.add_argument("--dry-rccl", action="store_true",
                     help="N > 1: only rendezvous, one halo exchange, one all-reduce and their checks; prints what RCCL "
                          "reports about the communicator (a 30-second run that tells init problems from perf problems)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure (CPU baseline, copy yardstick, other "
+                         "kernels and workloads, shard-boundary and count checks); a plain run times the K steps only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last step computed to DIR/<name>.npy (large planes: a fixed, "
+                         "seeded sample of rows)")
     args = ap.parse_args()
+    if not args.full:
+        args.no_extras = args.no_cpu_baseline = True
     ctx = Ctx(args)
     if args.dry_rccl:
         result = run_dry_rccl(ctx)

@@ -236,7 +236,7 @@ def test_bench_workloads_world2(workload, extra):
         env = dict(os.environ, RANK=str(rank), WORLD_SIZE="2", LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1",
                    MASTER_PORT=str(port), OMP_NUM_THREADS="1", XRS_RDZV_TIMEOUT="5")
         cmd = [sys.executable, os.path.join(ROOT, "tests", "bench_worker.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-               "--workload", workload, "--allow-host-halo", "--no-cpu-baseline", "--no-overlap"] + extra
+               "--workload", workload, "--full", "--allow-host-halo", "--no-cpu-baseline", "--no-overlap"] + extra
         procs.append(subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE))
     outs = []
     for p in procs:
@@ -271,7 +271,7 @@ def test_bench_headline_keeps_its_line_when_a_rank_hangs_in_the_extras(hang):
                    MASTER_PORT=str(port), OMP_NUM_THREADS="1", XRS_RDZV_TIMEOUT="5", XRS_BENCH_EXTRAS_TIMEOUT="8" if hang else "300",
                    XRS_BENCH_TEARDOWN_TIMEOUT="20", XRS_BENCH_TEST_HANG=hang)
         cmd = [sys.executable, os.path.join(ROOT, "tests", "bench_worker.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-               "--allow-host-halo", "--no-cpu-baseline", "--no-overlap", "--rows", "96", "--cols", "320", "--s64-size", "192",
+               "--full", "--allow-host-halo", "--no-cpu-baseline", "--no-overlap", "--rows", "96", "--cols", "320", "--s64-size", "192",
                "--zonal-size", "2048"]
         procs.append(subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE))
     outs = []
@@ -370,3 +370,34 @@ def test_bench_refuses_multi_gpu_without_rccl():
                        env=env, capture_output=True, timeout=120)
     assert p.returncode == 3, p.stderr.decode()[-2000:]
     assert b"refusing to run a multi-GPU benchmark without RCCL" in p.stderr
+
+
+def test_bench_plain_run_dumps_the_last_step(tmp_path):
+    """A plain one-GPU run (the C ABI answered by the oracle through tests/fake_hip.py) times the K steps and nothing else
+    (no CPU baseline, no informational figures), and --dump-outputs writes the two planes of the last step: finite (hillshade
+    without the raster's outermost row and column, where it has no value), the same from run to run, and what the CPU oracle
+    computes on the benchmark's DEM."""
+    import json
+    from oracle import xrs_oracle as orc
+    from tests import synth
+    from xrspatial_amd.convolution import circle_kernel
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    lines = []
+    for d in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "tests", "bench_worker.py"), "--steps", "3", "--warmup", "1", "--rows", "96",
+               "--cols", "320", "--dump-outputs", str(tmp_path / d)]
+        p = subprocess.run(cmd, env=env, capture_output=True, timeout=300)
+        assert p.returncode == 0, p.stderr.decode()[-3000:]
+        lines.append(json.loads([ln for ln in p.stdout.decode().splitlines() if ln.startswith("{")][-1]))
+    res = lines[0]
+    assert res["steps"] == 3 and res["warmup"] == 1 and res["ms_per_step"] > 0 and res["value"] > 0
+    assert "cpu_baseline" not in res and "unfused" not in res["config"] and res["roofline"]["measured_copy_gbs"] is None
+    dem = synth.asv_dem(96, 320, y0=0, total_rows=96)
+    want = {"hillshade": orc.hillshade(dem)[1:-1, 1:-1], "focal_mean_5x5": orc.focal_apply(dem, circle_kernel(1, 1, 2), 'mean')}
+    assert sorted(os.listdir(tmp_path / "a")) == ["focal_mean_5x5.npy", "hillshade.npy"]
+    for name, w in want.items():
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float32 and a.shape == w.shape
+        assert np.isfinite(a).all(), name
+        np.testing.assert_array_equal(a, b)
+        np.testing.assert_allclose(a, w, rtol=1e-5, atol=1e-6, err_msg=name)

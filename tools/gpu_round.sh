@@ -19,7 +19,7 @@ for s in $STEPS; do
       timeout 900 python tests/focal_large_check.py --out $OUT/focal_large.json > $OUT/focal_large.log 2>&1
       echo "rc=$?" >> $OUT/focal_large.log; grep -v "^ok " $OUT/focal_large.log | tail -60 ;;
     bench)
-      timeout 900 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; cat $OUT/bench.json; tail -5 $OUT/bench.err ;;
+      timeout 900 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; cat $OUT/bench.json; tail -5 $OUT/bench.err ;;
     pmc)
       timeout 900 python tools/pmc_profile.py copy_kernel,geodesic_slope,geodesic_aspect,pass_hill_focal5,pass_hill_slope_focal5,focal5_mean,hillshade,slope,aspect,focal25_mean,focal25_stats7,focal25_meanvarstd,focal25_minmaxrange,focal5_stats7,focal7_stats7,box25_stats7,box25_meanvarstd,box25_mean,annulus21_stats7,annulus21_mean,annulus25_mean,convolve21_annulus,terrain_hill_aspect_curv,zonal_1000,zonal_1000_scattered,zonal_5000 \
         --out $OUT/pmc.json --traffic $OUT/pmc_traffic.json > $OUT/pmc.log 2>&1; echo "pmc rc=$?"; tail -3 $OUT/pmc.log ;;
@@ -42,8 +42,8 @@ for s in $STEPS; do
       timeout 600 python tools/nan_probe.py > $OUT/nan_probe.log 2>&1; echo "nan rc=$?"; grep -E "focal25|fused|hillshade" $OUT/nan_probe.log | tail -30 ;;
     n1)
       # the one-GPU references of the strong-scaling workloads (bench.py quotes speedup_vs_n1 against them): -> profiles/n1_strong.json
-      timeout 600 python bench.py --workload s64 --steps 10 --warmup 3 --write-n1 $OUT/n1_strong.json > $OUT/bench_s64.json 2> $OUT/bench_s64.err; cat $OUT/bench_s64.json | head -c 400; echo
-      timeout 600 python bench.py --workload zonal32k --steps 10 --warmup 3 --write-n1 $OUT/n1_strong.json > $OUT/bench_zonal32k.json 2> $OUT/bench_zonal32k.err; cat $OUT/bench_zonal32k.json | head -c 400; echo
+      timeout 600 python bench.py --full --workload s64 --steps 10 --warmup 3 --write-n1 $OUT/n1_strong.json > $OUT/bench_s64.json 2> $OUT/bench_s64.err; cat $OUT/bench_s64.json | head -c 400; echo
+      timeout 600 python bench.py --full --workload zonal32k --steps 10 --warmup 3 --write-n1 $OUT/n1_strong.json > $OUT/bench_zonal32k.json 2> $OUT/bench_zonal32k.err; cat $OUT/bench_zonal32k.json | head -c 400; echo
       cat $OUT/n1_strong.json ;;
     fuzz)
       for seed in 51 52; do timeout 600 python tests/fuzz_parity.py --seed $seed --cases 1500 > $OUT/fuzz_s$seed.log 2>&1; tail -3 $OUT/fuzz_s$seed.log; done
@@ -67,7 +67,7 @@ for s in $STEPS; do
       (cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/maj_$TAG -o s -- python $ROOT/tools/majority_probe.py 32768 > /dev/null 2>&1)
       find /tmp/maj_$TAG -name "*kernel_stats.csv" -exec cp {} $OUT/majority_kernel_stats.csv \; ; cut -d, -f1-4 $OUT/majority_kernel_stats.csv | cut -c1-200 | head -24 ;;
     s64bench)
-      timeout 600 python bench.py --workload s64 --steps 10 --warmup 3 > $OUT/bench_s64.json 2> $OUT/bench_s64.err; cat $OUT/bench_s64.json ;;
+      timeout 600 python bench.py --full --workload s64 --steps 10 --warmup 3 > $OUT/bench_s64.json 2> $OUT/bench_s64.err; cat $OUT/bench_s64.json ;;
     *) echo "unknown step $s" ;;
   esac
   echo "== step $s took $(( $(date +%s) - t0 )) s"

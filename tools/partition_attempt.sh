@@ -43,7 +43,7 @@ EOF
         extra=""; [ $wl = s64 ] && extra="--s64-size 16384"; [ $wl = zonal32k ] && extra="--zonal-size 16384"
         echo "== bench.py --gpus $g --workload $wl $extra  (partitions of ONE chip: not a scaling curve)"
         timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node $g --master-addr 127.0.0.1 --master-port $((29600 + g)) \
-          bench.py --gpus $g --workload $wl $extra --steps 10 --warmup 3 --no-cpu-baseline --no-extras 2>&1 | tail -5
+          bench.py --gpus $g --workload $wl $extra --steps 10 --warmup 3 --full --no-cpu-baseline --no-extras 2>&1 | tail -5
       done
     done
     for g in 2 3 8; do
