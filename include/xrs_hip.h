@@ -253,6 +253,64 @@ int xrs_nan_moments_f32(const float *in_dev, int64_t n, void *moments32_dev, voi
 int xrs_hotspots_classify_f32(const float *mean_array_dev, signed char *out_dev, int64_t n,
                               float global_mean, float global_std, void *stream);
 
+/* -------------------------------------------------------------------- classify
+ * xrspatial.classify (reference: xrspatial/classify.py, CPU path).  Flat C-order rasters of n cells in their own dtype.
+ *  bin:        _cpu_bin (:153-187): out = float32(new_values[b]) for the bin b of every cell, NaN where there is none.
+ *              bins / new_values are float64 device arrays of n_bins; mode 0 = the reference's loop verbatim (any bins),
+ *              1 = count of bins below the cell, 2 = bisection (1 and 2 only for non-decreasing, NaN-free bins).
+ *  binary:     _cpu_binary (:31-41): 1 where the cell equals one of `values` (float64), else 0 (finite) / NaN (float).
+ *  finite_stats: { count, min, max, sum } of the finite cells (float64; min / max NaN when there is none);
+ *  sqdev:      { count, -, -, sum of (x - center)^2 } over the finite cells;  above: { count, -, -, sum } of finite x > threshold.
+ *  select:     the ranks[i]-th smallest finite cells (0-based int64 ranks, ascending, < the finite count, <= 64 per call),
+ *              as float64; MSB-first radix select over the order-preserving key.  n < 2^32.
+ *  max_breaks: the unique finite values uv[0..M) (-0.0 == +0.0), their gaps in the input dtype and the n_top largest gaps
+ *              by (gap, index) -> out = { M, (index, uv[index], uv[index + 1]) x n_top, uv[M-1], uv[0..n_top] }
+ *              (NaN / -1 where there is none); n_top < 0: out = { M, uv[0..M) } (n + 1 doubles).  n < 2^31.
+ * `work_dev` holds xrs_classify_workspace_bytes(n, values_f64) bytes (every entry point of this group fits in it). */
+size_t xrs_classify_workspace_bytes(int64_t n, int values_f64);
+int xrs_classify_to_f64(const void *in_dev, int dtype_code, double *out_dev, int64_t n, void *stream);
+int xrs_classify_bin_f32(const float *in_dev, float *out_dev, int64_t n, const double *bins_dev,
+                         const double *new_values_dev, int n_bins, int mode, void *stream);
+int xrs_classify_bin_f64(const double *in_dev, float *out_dev, int64_t n, const double *bins_dev,
+                         const double *new_values_dev, int n_bins, int mode, void *stream);
+int xrs_classify_bin_i32(const int32_t *in_dev, float *out_dev, int64_t n, const double *bins_dev,
+                         const double *new_values_dev, int n_bins, int mode, void *stream);
+int xrs_classify_bin_i64(const int64_t *in_dev, float *out_dev, int64_t n, const double *bins_dev,
+                         const double *new_values_dev, int n_bins, int mode, void *stream);
+int xrs_classify_binary_f32(const float *in_dev, float *out_dev, int64_t n, const double *values_dev, int n_values, void *stream);
+int xrs_classify_binary_f64(const double *in_dev, double *out_dev, int64_t n, const double *values_dev, int n_values,
+                            void *stream);
+int xrs_classify_binary_i8(const int8_t *in_dev, int8_t *out_dev, int64_t n, const double *values_dev, int n_values,
+                           void *stream);
+int xrs_classify_binary_u8(const uint8_t *in_dev, uint8_t *out_dev, int64_t n, const double *values_dev, int n_values,
+                           void *stream);
+int xrs_classify_binary_i16(const int16_t *in_dev, int16_t *out_dev, int64_t n, const double *values_dev, int n_values,
+                            void *stream);
+int xrs_classify_binary_u16(const uint16_t *in_dev, uint16_t *out_dev, int64_t n, const double *values_dev, int n_values,
+                            void *stream);
+int xrs_classify_binary_i32(const int32_t *in_dev, int32_t *out_dev, int64_t n, const double *values_dev, int n_values,
+                            void *stream);
+int xrs_classify_binary_u32(const uint32_t *in_dev, uint32_t *out_dev, int64_t n, const double *values_dev, int n_values,
+                            void *stream);
+int xrs_classify_binary_i64(const int64_t *in_dev, int64_t *out_dev, int64_t n, const double *values_dev, int n_values,
+                            void *stream);
+int xrs_classify_binary_u64(const uint64_t *in_dev, uint64_t *out_dev, int64_t n, const double *values_dev, int n_values,
+                            void *stream);
+int xrs_classify_finite_stats_f32(const float *in_dev, int64_t n, void *work_dev, double *out4_dev, void *stream);
+int xrs_classify_finite_stats_f64(const double *in_dev, int64_t n, void *work_dev, double *out4_dev, void *stream);
+int xrs_classify_sqdev_f32(const float *in_dev, int64_t n, double center, void *work_dev, double *out4_dev, void *stream);
+int xrs_classify_sqdev_f64(const double *in_dev, int64_t n, double center, void *work_dev, double *out4_dev, void *stream);
+int xrs_classify_above_f32(const float *in_dev, int64_t n, double threshold, void *work_dev, double *out4_dev, void *stream);
+int xrs_classify_above_f64(const double *in_dev, int64_t n, double threshold, void *work_dev, double *out4_dev, void *stream);
+int xrs_classify_select_f32(const float *in_dev, int64_t n, const int64_t *ranks_dev, int n_ranks, void *work_dev,
+                            size_t work_bytes, double *values_dev, void *stream);
+int xrs_classify_select_f64(const double *in_dev, int64_t n, const int64_t *ranks_dev, int n_ranks, void *work_dev,
+                            size_t work_bytes, double *values_dev, void *stream);
+int xrs_classify_max_breaks_f32(const float *in_dev, int64_t n, int n_top, void *work_dev, size_t work_bytes,
+                                double *out_dev, void *stream);
+int xrs_classify_max_breaks_f64(const double *in_dev, int64_t n, int n_top, void *work_dev, size_t work_bytes,
+                                double *out_dev, void *stream);
+
 /* -------------------------------------------------------------------- zonal
  * Per-zone partial reductions of one streaming pass over (zone index, value):
  * count (integer-exact), sum and sum of squares (float64), min, max.  Cells with

@@ -3,7 +3,8 @@
 Drop-in for the `xrspatial.*` functions on that path (same names, signatures, DataArray
 in/out): slope, aspect, hillshade, curvature, focal.mean / apply / focal_stats,
 convolution.convolve_2d / convolution_2d, multispectral ndvi / evi / savi (+ nbr, nbr2, ndmi),
-zonal.stats.  Python host code calling hand-written HIP kernels through the C ABI of
+zonal.stats, classify (binary, reclassify, equal_interval, quantile, percentiles, box_plot, std_mean,
+head_tail_breaks, maximum_breaks).  Python host code calling hand-written HIP kernels through the C ABI of
 libxrs_hip.so (include/xrs_hip.h); no PyTorch, CuPy, Numba or Triton involved.
 
     import xrspatial_amd as xrspatial        # numpy-backed DataArray in -> numpy-backed out
@@ -17,6 +18,8 @@ from .device import DeviceArray, empty_cache, synchronize  # noqa: F401
 from .utils import has_hip  # noqa: F401
 
 from .aspect import aspect  # noqa: F401
+from .classify import (binary, box_plot, equal_interval, head_tail_breaks, maximum_breaks, percentiles,  # noqa: F401
+                       quantile, reclassify, std_mean)
 from .curvature import curvature  # noqa: F401
 from .focal import mean  # noqa: F401
 from .fused import fuse  # noqa: F401
@@ -27,6 +30,6 @@ from .slope import slope  # noqa: F401
 from .zonal import crosstab as zonal_crosstab  # noqa: F401
 from .zonal import stats as zonal_stats  # noqa: F401
 
-from . import analytics, convolution, focal, multispectral, zonal  # noqa: F401
+from . import analytics, classify, convolution, focal, multispectral, zonal  # noqa: F401
 
 __version__ = "0.1.0"

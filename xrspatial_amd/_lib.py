@@ -135,6 +135,32 @@ _PROTOTYPES = {
     "xrs_zonal_group_f32": [c_void_p, c_void_p, c_int64, c_int, c_float, c_int, c_void_p, c_size_t, c_void_p, c_void_p],
     "xrs_zonal_group_f64": [c_void_p, c_void_p, c_int64, c_int, c_double, c_int, c_void_p, c_size_t, c_void_p, c_void_p],
     "xrs_zonal_backproject_f64": [c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p, c_void_p],
+    "xrs_classify_workspace_bytes": [c_int64, c_int],
+    "xrs_classify_to_f64": [c_void_p, c_int, c_void_p, c_int64, c_void_p],
+    "xrs_classify_bin_f32": [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_void_p],
+    "xrs_classify_bin_f64": [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_void_p],
+    "xrs_classify_bin_i32": [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_void_p],
+    "xrs_classify_bin_i64": [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_void_p],
+    "xrs_classify_binary_f32": [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p],
+    "xrs_classify_binary_f64": [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p],
+    "xrs_classify_binary_i8": [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p],
+    "xrs_classify_binary_u8": [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p],
+    "xrs_classify_binary_i16": [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p],
+    "xrs_classify_binary_u16": [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p],
+    "xrs_classify_binary_i32": [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p],
+    "xrs_classify_binary_u32": [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p],
+    "xrs_classify_binary_i64": [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p],
+    "xrs_classify_binary_u64": [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p],
+    "xrs_classify_finite_stats_f32": [c_void_p, c_int64, c_void_p, c_void_p, c_void_p],
+    "xrs_classify_sqdev_f32": [c_void_p, c_int64, c_double, c_void_p, c_void_p, c_void_p],
+    "xrs_classify_above_f32": [c_void_p, c_int64, c_double, c_void_p, c_void_p, c_void_p],
+    "xrs_classify_select_f32": [c_void_p, c_int64, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p],
+    "xrs_classify_max_breaks_f32": [c_void_p, c_int64, c_int, c_void_p, c_size_t, c_void_p, c_void_p],
+    "xrs_classify_finite_stats_f64": [c_void_p, c_int64, c_void_p, c_void_p, c_void_p],
+    "xrs_classify_sqdev_f64": [c_void_p, c_int64, c_double, c_void_p, c_void_p, c_void_p],
+    "xrs_classify_above_f64": [c_void_p, c_int64, c_double, c_void_p, c_void_p, c_void_p],
+    "xrs_classify_select_f64": [c_void_p, c_int64, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p],
+    "xrs_classify_max_breaks_f64": [c_void_p, c_int64, c_int, c_void_p, c_size_t, c_void_p, c_void_p],
     "xrs_comm_unique_id": [c_void_p],
     "xrs_comm_init_rank": [ctypes.POINTER(c_void_p), c_void_p, c_int, c_int],
     "xrs_comm_destroy": [c_void_p],
@@ -148,7 +174,7 @@ _PROTOTYPES = {
 }
 _RESTYPES = {"xrs_kxk_workspace_bytes": c_size_t, "xrs_focal_workspace_bytes": c_size_t, "xrs_zonal_majority_workspace_bytes": c_size_t,
              "xrs_zonal_mode_workspace_bytes": c_size_t,
-             "xrs_geodesic_workspace_bytes": c_size_t}
+             "xrs_geodesic_workspace_bytes": c_size_t, "xrs_classify_workspace_bytes": c_size_t}
 
 EXPORTED = tuple(_PROTOTYPES)
 

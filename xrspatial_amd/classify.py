@@ -1,0 +1,579 @@
+"""Raster classification: binary, reclassify and the data-driven classifiers equal_interval, quantile, percentiles,
+box_plot, std_mean, head_tail_breaks and maximum_breaks.  Reference: xrspatial/classify.py, its CPU path.
+
+Every per-cell pass runs in HIP (csrc/classify.hip): the bin pass (_cpu_bin), the membership pass (_cpu_binary), the
+finite min / max / count / sum and moment reductions, the exact order statistics (radix select) and the sort behind
+maximum_breaks.  What crosses to the host is a handful of scalars; from them the reference's own host formulas --
+restated below, quirks included -- build the bins, and the bin pass runs on the raster already resident in HBM.
+
+`natural_breaks` is not provided.  dask- and ShardedArray-backed rasters are accepted by the per-cell
+`binary` and `reclassify` only; the statistic-driven classifiers raise NotImplementedError for them.
+"""
+from __future__ import annotations
+
+import warnings
+
+import numpy as np
+
+from . import _lib
+from ._launch import finish, get_stream, percell_pipelined
+from ._xr import DataArray
+from .dataset_support import supports_dataset
+from .device import DTYPE_CODE, DeviceArray
+from .utils import ArrayTypeFunctionMapping, dask_blocks
+
+BIN_LITERAL, BIN_COUNT, BIN_SEARCH = 0, 1, 2
+_COUNT_MAX_BINS = 64                    # wave-uniform count up to this many bins, bisection above
+_SELECT_MAX_RANKS = 64
+_MAX_BREAKS_MAX_TOP = 64
+
+_BIN_SUFFIX = {np.dtype(np.float32): "f32", np.dtype(np.float64): "f64", np.dtype(np.int32): "i32",
+               np.dtype(np.int64): "i64"}
+_BINARY_SUFFIX = {np.dtype(t): s for t, s in ((np.float32, "f32"), (np.float64, "f64"), (np.int8, "i8"), (np.uint8, "u8"),
+                                               (np.int16, "i16"), (np.uint16, "u16"), (np.int32, "i32"),
+                                               (np.uint32, "u32"), (np.int64, "i64"), (np.uint64, "u64"))}
+
+
+def _wrap(out, name, agg):
+    return DataArray(out, name=name, dims=agg.dims, coords=agg.coords, attrs=agg.attrs)
+
+
+def _check_dtype(dtype):
+    if np.dtype(dtype) not in _BINARY_SUFFIX:
+        raise TypeError(f"classify: unsupported raster dtype {np.dtype(dtype)}")
+
+
+def _resident(data):
+    """(DeviceArray in the raster's own dtype, whether the caller expects NumPy back).  A NumPy raster is uploaded once."""
+    _lib.require_device()
+    if isinstance(data, DeviceArray):
+        _check_dtype(data.dtype)
+        return data, False
+    host = np.ascontiguousarray(data)
+    _check_dtype(host.dtype)
+    return DeviceArray.from_numpy(host, stream=get_stream()), True
+
+
+def _upload_f64(values):
+    arr = np.ascontiguousarray(values, dtype=np.float64)
+    return DeviceArray.from_numpy(arr if arr.size else np.zeros(1), stream=get_stream())
+
+
+def _as_f64(dev):
+    """float64 image of an integer raster on the device (exact below 2^53); float rasters are used as they are."""
+    if dev.dtype in (np.float32, np.float64):
+        return dev
+    out = DeviceArray(dev.shape, np.float64)
+    _lib.call("xrs_classify_to_f64", dev.ptr, DTYPE_CODE[dev.dtype], out.ptr, dev.size, get_stream())
+    return out
+
+
+# ------------------------------------------------------------------ the bin pass (_cpu_bin, classify.py:153-187)
+def bin_mode(bins):
+    """Which search of the bin kernel serves `bins` (float64): the literal loop unless they are non-decreasing and
+    NaN-free, where the loop is searchsorted-left."""
+    if bins.size and not np.isnan(bins).any() and bool(np.all(bins[1:] >= bins[:-1])):
+        return BIN_COUNT if bins.size <= _COUNT_MAX_BINS else BIN_SEARCH
+    return BIN_LITERAL
+
+
+def _bin_args(bins, new_values):
+    bins = np.asarray(bins)
+    new_values = np.asarray(new_values)
+    if bins.ndim != 1 or bins.size == 0:
+        raise IndexError("classify: bins must be a non-empty 1-D sequence")
+    b64 = bins.astype(np.float64)
+    # `out[y, x] = new_values[b]` rounds to float32 from new_values' own dtype; float32 -> float64 is exact
+    nv = new_values.astype(np.float32).astype(np.float64)
+    return b64, nv, bin_mode(b64)
+
+
+def _bin_device(dev, bins, new_values):
+    b64, nv, mode = _bin_args(bins, new_values)
+    src = dev if dev.dtype in _BIN_SUFFIX else _as_f64(dev)
+    bins_d, nv_d = _upload_f64(b64), _upload_f64(nv)
+    out = DeviceArray(dev.shape, np.float32)
+    _lib.call("xrs_classify_bin_" + _BIN_SUFFIX[src.dtype], src.ptr, out.ptr, src.size, bins_d.ptr, nv_d.ptr, b64.size, mode,
+              get_stream())
+    _lib.call("xrs_stream_sync", get_stream())          # the bins / temporaries go back to the pool
+    return out
+
+
+def _run_bin(data, bins, new_values):
+    if isinstance(data, np.ndarray) and data.dtype == np.float32:
+        b64, nv, mode = _bin_args(bins, new_values)
+        _lib.require_device()
+        bins_d, nv_d = _upload_f64(b64), _upload_f64(nv)
+        out = percell_pipelined("xrs_classify_bin_f32", [np.ascontiguousarray(data)], (bins_d.ptr, nv_d.ptr, b64.size, mode))
+        if out is not None:
+            return out
+    dev, like_numpy = _resident(data)
+    return finish(_bin_device(dev, bins, new_values), like_numpy)
+
+
+def _run_sharded_bin(data, bins, new_values):
+    if data.dtype not in _BIN_SUFFIX:
+        raise NotImplementedError(f"reclassify: row-sharded {data.dtype} rasters are not supported")
+    b64, nv, mode = _bin_args(bins, new_values)
+    bins_d, nv_d = _upload_f64(b64), _upload_f64(nv)
+    out = data.like(np.float32)
+    _lib.call("xrs_classify_bin_" + _BIN_SUFFIX[data.dtype], data.ptr, out.ptr, out.size, bins_d.ptr, nv_d.ptr, b64.size,
+              mode, get_stream())
+    _lib.call("xrs_stream_sync", get_stream())
+    return out
+
+
+# ------------------------------------------------------------------ binary (_cpu_binary, classify.py:31-41)
+def _binary_device(dev, values):
+    vals = np.asarray(values).astype(np.float64).ravel()
+    vals_d = _upload_f64(vals)
+    out = DeviceArray(dev.shape, dev.dtype)
+    _lib.call("xrs_classify_binary_" + _BINARY_SUFFIX[dev.dtype], dev.ptr, out.ptr, dev.size, vals_d.ptr, vals.size,
+              get_stream())
+    _lib.call("xrs_stream_sync", get_stream())
+    return out
+
+
+def _run_binary(data, values):
+    if isinstance(data, np.ndarray) and data.dtype == np.float32:
+        _lib.require_device()
+        vals = np.asarray(values).astype(np.float64).ravel()
+        vals_d = _upload_f64(vals)
+        out = percell_pipelined("xrs_classify_binary_f32", [np.ascontiguousarray(data)], (vals_d.ptr, vals.size))
+        if out is not None:
+            return out
+    dev, like_numpy = _resident(data)
+    return finish(_binary_device(dev, values), like_numpy)
+
+
+def _run_sharded_binary(data, values):
+    _check_dtype(data.dtype)
+    vals = np.asarray(values).astype(np.float64).ravel()
+    vals_d = _upload_f64(vals)
+    out = data.like(data.dtype)
+    _lib.call("xrs_classify_binary_" + _BINARY_SUFFIX[np.dtype(data.dtype)], data.ptr, out.ptr, out.size, vals_d.ptr,
+              vals.size, get_stream())
+    _lib.call("xrs_stream_sync", get_stream())
+    return out
+
+
+# ------------------------------------------------------------------ device statistics of one resident raster
+class _Stats:
+    """Finite-cell statistics of a resident raster, computed on the device; only scalars come back."""
+
+    def __init__(self, dev):
+        self.dev = dev
+        self.dtype = dev.dtype                 # dtype of `data[np.isfinite(data)]` in the reference
+        self.src = _as_f64(dev)
+        self.suffix = "f32" if self.src.dtype == np.float32 else "f64"
+        self.n = dev.size
+        # reductions and the select need a fixed few hundred KiB (the workspace of a 1-cell call); the sort of
+        # maximum_breaks a multiple of the raster, allocated when it runs
+        self.work = DeviceArray((_lib.load().xrs_classify_workspace_bytes(1, int(self.suffix == "f64")),), np.uint8)
+        self.out = DeviceArray((4,), np.float64)
+        self._moments = None
+
+    def _reduce(self, fn, *arg):
+        if self.n == 0:
+            return np.array([0.0, np.nan, np.nan, 0.0])
+        _lib.call(f"xrs_classify_{fn}_{self.suffix}", self.src.ptr, self.n, *arg, self.work.ptr, self.out.ptr, get_stream())
+        return self.out.get(get_stream())
+
+    def moments(self):
+        """(count, min, max, sum) of the finite cells."""
+        if self._moments is None:
+            c, mn, mx, s = self._reduce("finite_stats")
+            self._moments = (int(c), float(mn), float(mx), float(s))
+        return self._moments
+
+    @property
+    def count(self):
+        return self.moments()[0]
+
+    def sqdev(self, center):
+        return float(self._reduce("sqdev", float(center))[3])
+
+    def head(self, threshold):
+        """(count, mean) of the finite cells > threshold (float64 sum / count)."""
+        r = self._reduce("above", float(threshold))
+        return int(r[0]), (float(r[3]) / r[0] if r[0] else float("nan"))
+
+    def select(self, ranks):
+        """{rank: value} of the 0-based order statistics of the finite cells (exact, in the raster's dtype)."""
+        ranks = np.unique(np.asarray(ranks, dtype=np.int64))
+        vals = {}
+        for i in range(0, ranks.size, _SELECT_MAX_RANKS):
+            part = ranks[i:i + _SELECT_MAX_RANKS]
+            r_d = DeviceArray.from_numpy(part, stream=get_stream())
+            v_d = DeviceArray((part.size,), np.float64)
+            _lib.call(f"xrs_classify_select_{self.suffix}", self.src.ptr, self.n, r_d.ptr, part.size, self.work.ptr,
+                      self.work.nbytes, v_d.ptr, get_stream())
+            vals.update(zip(part.tolist(), v_d.get(get_stream()).tolist()))
+        return vals
+
+    def max_breaks(self, n_top):
+        """(M, picks [(index, uv[index], uv[index + 1])], uv[M - 1], uv[:n_top + 1]); n_top < 0: (M, all of uv)."""
+        if n_top < 0:
+            out = DeviceArray((self.n + 1,), np.float64)
+        else:
+            out = DeviceArray((2 + 4 * n_top + 1,), np.float64)
+        work = DeviceArray((_lib.load().xrs_classify_workspace_bytes(self.n, int(self.suffix == "f64")),), np.uint8)
+        _lib.call(f"xrs_classify_max_breaks_{self.suffix}", self.src.ptr, self.n, int(n_top), work.ptr, work.nbytes,
+                  out.ptr, get_stream())
+        if n_top < 0:
+            m = int(DeviceArray((1,), np.float64, _ptr=out.ptr, _base=out).get(get_stream())[0])
+            host = DeviceArray((m + 1,), np.float64, _ptr=out.ptr, _base=out).get(get_stream())
+            return m, host[1:]
+        host = out.get(get_stream())
+        m = int(host[0])
+        picks = [(int(host[1 + 3 * j]), host[2 + 3 * j], host[3 + 3 * j]) for j in range(n_top)]
+        return m, picks, host[1 + 3 * n_top], host[2 + 3 * n_top: 2 + 3 * n_top + n_top + 1]
+
+
+# ------------------------------------------------------------------ numpy's percentile, method 'linear'
+def _lerp(a, b, t):
+    """numpy's _lerp (lib/_function_base_impl.py): a + (b - a) * t, or b - (b - a) * (1 - t) where t >= 0.5."""
+    diff_b_a = np.subtract(b, a)
+    lerp = np.asanyarray(np.add(a, diff_b_a * t))
+    np.subtract(b, diff_b_a * (1 - t), out=lerp, where=t >= 0.5, casting='unsafe', dtype=type(lerp.dtype))
+    if lerp.ndim == 0:
+        lerp = lerp[()]
+    return lerp
+
+
+def _quantile_is_valid(q):
+    if q.ndim == 1 and q.size < 10:
+        for i in range(q.size):
+            if not (0.0 <= q[i] <= 1.0):
+                return False
+    elif not (np.all(0 <= q) and np.all(q <= 1)):
+        return False
+    return True
+
+
+def percentile_indexes(n, q_raw, dtype):
+    """The rank arithmetic of np.percentile(a, q_raw) for a 1-D `a` of n cells of `dtype`:
+    (q, virtual index, previous / next ranks as intp arrays with numpy's -1 for 'the last cell')."""
+    dtype = np.dtype(dtype)
+    q = np.true_divide(q_raw, dtype.type(100) if dtype.kind == "f" else 100)
+    q = np.asanyarray(q)
+    if not _quantile_is_valid(q):
+        raise ValueError("Percentiles must be in the range [0, 100]")
+    virtual = np.asanyarray((n - 1) * q)
+    prev = np.asanyarray(np.floor(virtual))
+    nxt = np.asanyarray(prev + 1)
+    above = virtual >= n - 1
+    if above.any():
+        prev[above] = -1
+        nxt[above] = -1
+    below = virtual < 0
+    if below.any():
+        prev[below] = 0
+        nxt[below] = 0
+    if dtype.kind == "f":
+        nans = np.isnan(virtual)
+        if nans.any():
+            prev[nans] = -1
+            nxt[nans] = -1
+    return q, virtual, prev.astype(np.intp), nxt.astype(np.intp)
+
+
+def percentile_from_order_stats(n, q_raw, dtype, value_at):
+    """np.percentile(a, q_raw) (method 'linear') of the n finite cells of `dtype`, from `value_at(ranks) -> {rank: value}`
+    (0-based order statistics).  Result dtype and rounding as numpy's: the lerp runs in the dtype numpy picks."""
+    dtype = np.dtype(dtype)
+    if n == 0:
+        return np.percentile(np.empty(0, dtype), q_raw)          # numpy's own error for an empty sample
+    q, virtual, prev, nxt = percentile_indexes(n, q_raw, dtype)
+    rank = lambda idx: np.where(idx < 0, n + idx, idx)         # noqa: E731  (-1: the last cell after the partition)
+    vals = value_at(np.concatenate([rank(prev).ravel(), rank(nxt).ravel()]))
+
+    def take(idx):
+        arr = np.asarray([vals[int(i)] for i in rank(idx).ravel()], dtype=np.float64).astype(dtype).reshape(idx.shape)
+        return arr[()]
+
+    gamma = np.asanyarray(virtual - prev)
+    gamma = np.asanyarray(gamma, dtype=virtual.dtype).reshape(virtual.shape)
+    return _lerp(take(prev), take(nxt), gamma)
+
+
+# ------------------------------------------------------------------ host bin builders (reference formulas)
+def equal_interval_bins(min_data, max_data, k):
+    """_run_equal_interval (classify.py:805-835) from the finite min / max: (bins, new_values)."""
+    width = (max_data - min_data) / k
+    cuts = np.arange(min_data + width, max_data + width, width)
+    l_cuts = cuts.shape[0]
+    if l_cuts > k:
+        cuts = cuts[0:k]
+    cuts[-1] = max_data
+    return cuts, np.arange(l_cuts)
+
+
+def quantile_percents(k):
+    """The percent list of _run_quantile (classify.py:436-445)."""
+    w = 100.0 / k
+    p = np.arange(w, 100 + w, w)
+    if p[-1] > 100.0:
+        p[-1] = 100.0
+    return p
+
+
+def quantile_bins(q, k):
+    """quantile's host side (classify.py:436-445, 526-532) from the percentiles `q` (numpy's result): (bins, new_values)."""
+    q = np.unique(q)
+    k_q = q.shape[0]
+    if k_q < k:
+        print("Quantile Warning: Not enough unique values"
+              "for k classes (using {} bins)".format(k_q))
+        k = k_q
+    return q, np.arange(k)
+
+
+def percentiles_bins(q, max_v):
+    """percentiles' host side (classify.py:1145-1180) from the percentiles and the finite max: (bins, new_values)."""
+    q_np = np.asarray(np.unique(q))
+    bins = np.sort(np.unique(np.append(q_np, max_v)))
+    return bins, np.arange(len(bins))
+
+
+def box_plot_bins(q1, q2, q3, max_v, hinge):
+    """_run_box_plot (classify.py:1260-1292) from the quartiles and the finite max: (bins, new_values)."""
+    iqr = q3 - q1
+    raw_bins = [q1 - hinge * iqr, q1, q2, q3, q3 + hinge * iqr, max_v]
+    bins = np.sort(np.unique(raw_bins))
+    bins = bins[bins <= max_v]
+    if bins[-1] < max_v:
+        bins = np.append(bins, max_v)
+    return bins, np.arange(len(bins))
+
+
+def std_mean_bins(mean_v, std_v, max_v):
+    """_run_std_mean (classify.py:906-931) from the finite mean / population std / max: (bins, new_values)."""
+    bins = np.sort(np.unique([mean_v - 2 * std_v, mean_v - std_v, mean_v + std_v, mean_v + 2 * std_v, max_v]))
+    return bins, np.arange(len(bins))
+
+
+def head_tail_bins(head, n_all, max_v, dtype):
+    """_compute_head_tail_bins (classify.py:973-987) driven by `head(t) -> (count, mean)` of the finite cells > t."""
+    bins = []
+    cnt, mean_v = head(-np.inf)
+    while cnt > 1:
+        bins.append(mean_v)
+        h_cnt, h_mean = head(mean_v)
+        if h_cnt == 0 or h_cnt / cnt > 0.40:
+            break
+        cnt, mean_v = h_cnt, h_mean
+    if not bins:
+        if n_all == 0:
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore", RuntimeWarning)
+                bins = [float(np.nanmean(np.empty(0, dtype)))]
+            np.nanmax(np.empty(0, dtype))                    # numpy's own error: no finite cell
+        bins = [mean_v]
+    bins.append(float(max_v))
+    return np.array(bins), np.arange(len(bins))
+
+
+def maximum_break_bins_from_picks(m, picks, last, head, k, dtype):
+    """_compute_maximum_break_bins (classify.py:1183-1195) for 2 <= k: from the number of unique values m, the picked
+    gaps (index, uv[index], uv[index + 1]), uv[-1] and the first unique values `head`."""
+    dtype = np.dtype(dtype)
+    if m < k:
+        return np.asarray(head[:m]).astype(dtype), np.arange(m)
+    idx = sorted(p for p in picks if p[0] >= 0)
+    bins = np.array([(dtype.type(a) + dtype.type(b)) / 2.0 for _, a, b in idx])
+    bins = np.append(bins, float(dtype.type(last)))
+    return bins, np.arange(len(bins))
+
+
+def maximum_break_bins_from_unique(uv, k):
+    """The same for any k, from every unique value (k < 2: the reference keeps np.argsort(...)[-n:] with n <= 0)."""
+    if len(uv) < k:
+        return uv, np.arange(len(uv))
+    diffs = np.diff(uv)
+    n_gaps = min(k - 1, len(diffs))
+    top_indices = np.argsort(diffs, kind='stable')[-n_gaps:]
+    top_indices.sort()
+    bins = np.array([(uv[i] + uv[i + 1]) / 2.0 for i in top_indices])
+    bins = np.append(bins, float(uv[-1]))
+    return bins, np.arange(len(bins))
+
+
+# ------------------------------------------------------------------ the statistic-driven runners
+def _nan_warning(msg):
+    warnings.warn(msg, RuntimeWarning, stacklevel=4)
+
+
+def _clean_dtype(dtype):
+    """dtype of `np.where(np.isinf(data), np.nan, data)`: a float raster keeps its dtype, an integer one is float64."""
+    return np.dtype(dtype) if np.dtype(dtype).kind == "f" else np.dtype(np.float64)
+
+
+def _finite_max(st):
+    n, _, mx, _ = st.moments()
+    if n == 0:
+        _nan_warning("All-NaN slice encountered")
+    return mx
+
+
+def _classified(st, like_numpy, bins, new_values):
+    return finish(_bin_device(st.dev, bins, new_values), like_numpy)
+
+
+def _run_equal_interval(data, k):
+    dev, like_numpy = _resident(data)
+    st = _Stats(dev)
+    n, mn, mx, _ = st.moments()
+    if n == 0:
+        _nan_warning("All-NaN slice encountered")
+        _nan_warning("All-NaN slice encountered")
+    bins, nv = equal_interval_bins(mn, mx, k)
+    return _classified(st, like_numpy, bins, nv)
+
+
+def _percentiles_of(st, q_raw, dtype):
+    return percentile_from_order_stats(st.count, q_raw, dtype, st.select)
+
+
+def _run_quantile(data, k):
+    dev, like_numpy = _resident(data)
+    st = _Stats(dev)
+    q = _percentiles_of(st, quantile_percents(k), st.dtype)
+    bins, nv = quantile_bins(q, k)
+    return _classified(st, like_numpy, bins, nv)
+
+
+def _run_percentiles(data, pct):
+    dev, like_numpy = _resident(data)
+    st = _Stats(dev)
+    q = np.unique(_percentiles_of(st, pct, st.dtype))
+    bins, nv = percentiles_bins(q, _finite_max(st))
+    return _classified(st, like_numpy, bins, nv)
+
+
+def _run_box_plot(data, hinge):
+    dev, like_numpy = _resident(data)
+    st = _Stats(dev)
+    dt = _clean_dtype(st.dtype)
+    q1, q2, q3 = (float(_percentiles_of(st, p, dt)) for p in (25, 50, 75))
+    bins, nv = box_plot_bins(q1, q2, q3, _finite_max(st), hinge)
+    return _classified(st, like_numpy, bins, nv)
+
+
+def _run_std_mean(data):
+    dev, like_numpy = _resident(data)
+    st = _Stats(dev)
+    n, _, mx, s = st.moments()
+    if n == 0:
+        _nan_warning("Mean of empty slice")
+        _nan_warning("Degrees of freedom <= 0 for slice.")
+        _nan_warning("All-NaN slice encountered")
+        mean_v = std_v = float("nan")
+    else:
+        mean_v = s / n
+        std_v = float(np.sqrt(st.sqdev(mean_v) / n))
+    bins, nv = std_mean_bins(mean_v, std_v, mx)
+    return _classified(st, like_numpy, bins, nv)
+
+
+def _run_head_tail_breaks(data):
+    dev, like_numpy = _resident(data)
+    st = _Stats(dev)
+    n, _, mx, _ = st.moments()
+    bins, nv = head_tail_bins(st.head, n, mx, st.dtype)
+    return _classified(st, like_numpy, bins, nv)
+
+
+def _run_maximum_breaks(data, k):
+    dev, like_numpy = _resident(data)
+    st = _Stats(dev)
+    dtype = st.dtype
+    if st.n == 0:
+        bins, nv = np.empty(0, dtype), np.arange(0)
+    elif 2 <= k <= _MAX_BREAKS_MAX_TOP + 1:
+        m, picks, last, head = st.max_breaks(k - 1)
+        bins, nv = maximum_break_bins_from_picks(m, picks, last, head, k, dtype)
+    else:
+        _, uv = st.max_breaks(-1)
+        bins, nv = maximum_break_bins_from_unique(uv.astype(dtype), k)
+    if len(bins) == 0:                 # no finite cell: the reference's loop never reads a bin, every cell is NaN
+        bins, nv = np.zeros(1), np.zeros(1)
+    return _classified(st, like_numpy, bins, nv)
+
+
+def _statistic_mapper(run):
+    return ArrayTypeFunctionMapping(numpy_func=run, hip_func=run)
+
+
+# ------------------------------------------------------------------ public functions
+@supports_dataset
+def binary(agg, values, name='binary'):
+    """1 where a cell equals one of `values`, 0 for every other finite cell, NaN for the other non-finite cells; the
+    output keeps the input dtype.  Same signature and results as `xrspatial.classify.binary` (CPU path)."""
+    mapper = ArrayTypeFunctionMapping(numpy_func=_run_binary, hip_func=_run_binary, sharded_func=_run_sharded_binary,
+                                      dask_func=dask_blocks(lambda d: _run_binary(d, values)))
+    m = mapper(agg)
+    out = m(agg.data) if m is mapper.dask_func else m(agg.data, values)
+    return _wrap(out, name, agg)
+
+
+@supports_dataset
+def reclassify(agg, bins, new_values, name='reclassify'):
+    """new_values[b] (float32) for the bin b of every cell: the first b with value <= bins[b] for sorted bins, the
+    reference's bisection verbatim for any others.  Same signature and results as `xrspatial.classify.reclassify`."""
+    if len(bins) != len(new_values):
+        raise ValueError('bins and new_values mismatch. Should have same length.')
+    mapper = ArrayTypeFunctionMapping(numpy_func=_run_bin, hip_func=_run_bin, sharded_func=_run_sharded_bin,
+                                      dask_func=dask_blocks(lambda d: _run_bin(d, bins, new_values)))
+    m = mapper(agg)
+    out = m(agg.data) if m is mapper.dask_func else m(agg.data, bins, new_values)
+    return _wrap(out, name, agg)
+
+
+@supports_dataset
+def quantile(agg, k=4, name='quantile'):
+    """Classes of equal count: bins at the k quantiles of the finite cells (exact order statistics on the device,
+    numpy's 'linear' interpolation).  Same signature and results as `xrspatial.classify.quantile`."""
+    return _wrap(_statistic_mapper(_run_quantile)(agg)(agg.data, k), name, agg)
+
+
+@supports_dataset
+def equal_interval(agg, k=5, name='equal_interval'):
+    """k classes of equal width between the finite min and max.  Same results as `xrspatial.classify.equal_interval`."""
+    return _wrap(_statistic_mapper(_run_equal_interval)(agg)(agg.data, k), name, agg)
+
+
+@supports_dataset
+def std_mean(agg, name='std_mean'):
+    """Bins at mean -/+ 1 and 2 standard deviations and the max of the finite cells (`xrspatial.classify.std_mean`)."""
+    return _wrap(_statistic_mapper(_run_std_mean)(agg)(agg.data), name, agg)
+
+
+@supports_dataset
+def head_tail_breaks(agg, name='head_tail_breaks'):
+    """Head/tail breaks: repeated means of the values above the previous mean while the head holds <= 40 % of them
+    (`xrspatial.classify.head_tail_breaks`)."""
+    return _wrap(_statistic_mapper(_run_head_tail_breaks)(agg)(agg.data), name, agg)
+
+
+@supports_dataset
+def percentiles(agg, pct=None, name='percentiles'):
+    """Bins at the given percentiles (default 1, 10, 50, 90, 99) of the finite cells plus their max
+    (`xrspatial.classify.percentiles`)."""
+    if pct is None:
+        pct = [1, 10, 50, 90, 99]
+    return _wrap(_statistic_mapper(_run_percentiles)(agg)(agg.data, pct), name, agg)
+
+
+@supports_dataset
+def maximum_breaks(agg, k=5, name='maximum_breaks'):
+    """Bins at the midpoints of the k-1 widest gaps between the sorted unique finite values, plus their max
+    (`xrspatial.classify.maximum_breaks`)."""
+    return _wrap(_statistic_mapper(_run_maximum_breaks)(agg)(agg.data, k), name, agg)
+
+
+@supports_dataset
+def box_plot(agg, hinge=1.5, name='box_plot'):
+    """Bins at q1 - hinge*iqr, q1, q2, q3, q3 + hinge*iqr and the finite max, those above the max dropped
+    (`xrspatial.classify.box_plot`)."""
+    return _wrap(_statistic_mapper(_run_box_plot)(agg)(agg.data, hinge), name, agg)
