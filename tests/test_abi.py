@@ -86,18 +86,19 @@ def test_oracle_is_used_only_by_tests_smoke_and_the_cpu_baseline():
     assert all(h > entry.index("def smoke") for h in [m.start() for m in imp.finditer(entry)])
 
 
-def test_build_id_covers_every_source_and_header():
-    """xrs_build_id() is a hash of the files the Makefile lists (SRCS + SRCS_AB + HDRS): bench.py, the PMC table and every log key
+def test_build_id_hashes_every_source_and_header():
+    """xrs_build_id() is a hash of the files the Makefile lists (SRCS + HDRS): bench.py, the PMC table and every log key
     their numbers by it, so a kernel source or header that is not listed would change the library without changing the id."""
     import glob
     import re
     csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "xrspatial_amd", "csrc")
     mk = open(os.path.join(csrc, "Makefile")).read().replace("\\\n", " ")
     listed = set()
-    for var in ("SRCS", "SRCS_AB", "HDRS"):
+    for var in ("SRCS", "HDRS"):
         m = re.search(r"^%s\s*=\s*(.*)$" % var, mk, re.M)
         assert m, var
         listed |= {os.path.basename(w) for w in m.group(1).split()}
+    assert re.search(r"cat \$\(SRCS\) \$\(HDRS\) \| sha256sum", mk), "the build id must hash SRCS and HDRS"
     on_disk = {os.path.basename(p) for ext in ("*.hip", "*.h") for p in glob.glob(os.path.join(csrc, ext))}
     assert on_disk <= listed, f"not in the Makefile's SRCS / HDRS (so not in the build id): {sorted(on_disk - listed)}"
     # ... and every quoted include resolves to a listed file

@@ -504,14 +504,13 @@ int launch_box_sep(const float *in, float *out_sum, float *out_mean, float *out_
     const long slots = (long)n_cu * wg_cu;
     int best = 256;
     double best_cost = 1e300;
-    const char *force = ab_env("XRS_BOX_TILE_ROWS");
     for (int tr = 128; tr <= 512; tr += 32) {
         const long ty = (rows + tr - 1) / tr;
         const long rounds = (a.groups_x * ty + slots - 1) / slots;
         const double cost = (double)rounds * (double)(tr + 2 * a.ry);
         if (cost < best_cost) { best_cost = cost; best = tr; }
     }
-    a.tile_rows = force && atoi(force) >= 8 ? atoi(force) : best;
+    a.tile_rows = best;
     a.tiles_y = (rows + a.tile_rows - 1) / a.tile_rows;
     a.rim_first = 1;
     const long grid = RimFirst(a.groups_x, a.tiles_y, a.rim_first).grid();

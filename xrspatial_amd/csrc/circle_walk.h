@@ -162,7 +162,7 @@ __device__ __forceinline__ void ring_rotate(float (&a)[K][N]) {                /
 // out in whole ROUNDS of resident workgroups: 4096 workgroups on 768 slots are 5.3 rounds and cost 6.  Chosen per launch:
 // the tile height whose (rounds x input rows per tile) is smallest, for `groups_x` workgroups per tile row, `wg_per_cu`
 // resident workgroups per CU and rounds of `u` rows.  Measured on 16384^2, radius 12 (profiles/r03): moments 1.65 ms with
-// 128-row tiles, 1.36 with 256, 2.2 with 384.  XRS_WALK_TILE_ROWS overrides (A/B runs).
+// 128-row tiles, 1.36 with 256, 2.2 with 384.
 // resident 256-thread workgroups per CU of a kernel, as the runtime computes it from the kernel's registers and LDS
 template <typename K>
 inline int walk3_wg_per_cu(K kernel_fn, int fallback) {
@@ -172,8 +172,6 @@ inline int walk3_wg_per_cu(K kernel_fn, int fallback) {
 }
 
 inline int walk3_tile_base(long rows, long groups_x, int radius, int u, int wg_per_cu) {
-    const char *e = ab_env("XRS_WALK_TILE_ROWS");
-    if (e && atoi(e) >= 16) return atoi(e);
     static thread_local int n_cu = 0;
     if (!n_cu) {
         int dev = 0;
@@ -200,15 +198,11 @@ inline int walk3_tile_base(long rows, long groups_x, int radius, int u, int wg_p
 
 struct RimFirst {
     long gw, gh, n_rim, n_all;
-    // mode 1: rim first; 0: row-major tiles in one contiguous band per XCD (rounds 1-2: XRS_RIM_FIRST=0, A/B runs)
+    // mode 1: rim first (every launch); 0: row-major tiles in one contiguous band per XCD (the order of rounds 1-2)
     __host__ __device__ __forceinline__ RimFirst(long gw_, long gh_, int mode = 1) : gw(gw_), gh(gh_) {      // (forced: a CALL of this
                                                                                                         //  constructor from the largest kernels faulted at address 0)
         n_all = gw * gh;
         n_rim = mode == 0 ? -1 : (gw <= 2 || gh <= 2) ? n_all : 2 * gw + 2 * (gh - 2);
-    }
-    static int mode_from_env() {
-        const char *e = ab_env("XRS_RIM_FIRST");
-        return e && e[0] == '0' ? 0 : 1;
     }
     __host__ long grid() const { return n_rim < 0 ? xcd_grid(n_all, 0) : n_rim + xcd_grid(n_all - n_rim, 0); }
     __device__ __forceinline__ bool locate(long block, long &gy, long &gx) const {

@@ -177,9 +177,6 @@ struct ExtWalk {
         const long off = out_off;                             // (wave-uniform row address + 4 * lane)
         out_off += g.ld_out;
         if (EDGE && (x >= g.cols || yo >= y_end)) return;
-#ifdef XRS_FLOOR_NO_STORES                                     // (tools/floor_probe.sh: the walk without its output streams)
-        if (g.rows >= 0) return;
-#endif
         if (a.out_max) st_row_nt(uniform_ptr(a.out_max + off), 4u * (unsigned)lane, hi);
         if (a.out_min) st_row_nt(uniform_ptr(a.out_min + off), 4u * (unsigned)lane, lo);
         if (a.out_range) st_row_nt(uniform_ptr(a.out_range + off), 4u * (unsigned)lane, hi - lo);
@@ -217,15 +214,8 @@ struct ExtWalk {
             slot_out = slot_out + 1 == C::RB ? 0 : slot_out + 1;
         }
         float lo1[R + 1], hi1[R + 1], lo2[R + 1], hi2[R + 1];
-#ifdef XRS_FLOOR_NO_ARITH                                      // (tools/floor_probe.sh: the DMA ring and the stores, no reads / extrema)
-#pragma unroll
-        for (int h = 0; h <= R; ++h) { lo1[h] = hi1[h] = lo2[h] = hi2[h] = 0.0f; }
-        if (g.rows < 0)
-#endif
-        {
         row_levels(row1, lo1, hi1);
         row_levels(row2, lo2, hi2);
-        }
         if (EDGE) {
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
@@ -313,7 +303,7 @@ int launch_ext(ExtArgs &a, const double *kernel, hipStream_t s) {
     if (!wg_per_cu) wg_per_cu = walk3_wg_per_cu(focal_ext_kernel<R, Shape, 3>, XRS_EXT_WAVES);
     a.tile_rows = C::nin(walk3_tile_base(g.rows, g.tiles_x, R, C::U, wg_per_cu)) - 2 * R;
     g.n_tiles = g.tiles_x * ((g.rows + a.tile_rows - 1) / a.tile_rows);
-    a.rim_first = RimFirst::mode_from_env();
+    a.rim_first = 1;
     const long grid = RimFirst(g.tiles_x, g.n_tiles / g.tiles_x, a.rim_first).grid();
     if (grid > 0x7fffffffL) return fail("focal max / min: raster too large for one launch");
     const int n_out = (a.out_max != nullptr) + (a.out_min != nullptr) + (a.out_range != nullptr);
@@ -340,9 +330,7 @@ int XRS_EXT_ENTRY(const float *in, float *out_max, float *out_min, float *out_ra
     a.out_max = out_max; a.out_min = out_min; a.out_range = out_range;
     switch (krows / 2) {
 #define XRS_EXT_CASE(RR) case RR: return launch_ext<RR, XRS_EXT_SHAPE>(a, kernel, s);
-#ifndef XRS_EXT_PROBE
         XRS_EXT_CASE(4) XRS_EXT_CASE(5) XRS_EXT_CASE(6) XRS_EXT_CASE(7) XRS_EXT_CASE(8) XRS_EXT_CASE(9) XRS_EXT_CASE(10) XRS_EXT_CASE(11)
-#endif
         XRS_EXT_CASE(12)
 #undef XRS_EXT_CASE
         default: return -1;

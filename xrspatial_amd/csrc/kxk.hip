@@ -935,12 +935,13 @@ int launch_mean_fast(const KxkArgs &a, size_t lds, hipStream_t s) {
     return 0;
 }
 
-template <int KH, int KW, int RB>
-int launch_mean_direct_rb(KxkArgs a, hipStream_t s) {
+template <int KH, int KW>
+int launch_mean_direct(KxkArgs a, hipStream_t s) {
+    constexpr int RB = 4;
     a.n_tiles = a.tiles_x * ((a.rows + 4 * RB - 1) / (4 * RB));
     // np.ones((3, 3)) as a compile-time mask: 0.41 -> 0.37 ms.  (The same for the 5x5 masks made the stand-alone kernel
     // spill at its 128-register budget -- 0.42 -> 1.80 ms -- so they keep the run-time mask; profiles/r01/cmask2_ab_r01.log.)
-    constexpr bool SPECIALISE = KH == 3 && KW == 3 && RB == 4;
+    constexpr bool SPECIALISE = KH == 3 && KW == 3;
     constexpr unsigned BOX = SPECIALISE ? (1u << (KH * KW)) - 1u : 0u;
     unsigned mask = 0;
     for (int ky = 0; ky < KH; ++ky) mask |= (unsigned)a.mask_rows[ky] << (ky * KW);
@@ -951,13 +952,6 @@ int launch_mean_direct_rb(KxkArgs a, hipStream_t s) {
         hipLaunchKernelGGL((focal_mean_direct_kernel<KH, KW, RB>), grid, dim3(256), 0, s, a);
     XRS_LAUNCH_CHECK();
     return 0;
-}
-
-template <int KH, int KW>
-int launch_mean_direct(const KxkArgs &a, hipStream_t s) {
-    const char *e = ab_env("XRS_FOCAL_RB");          // A/B knob: rows per wave (default 4)
-    if (e && e[0] == '2') return launch_mean_direct_rb<KH, KW, 2>(a, s);
-    return launch_mean_direct_rb<KH, KW, 4>(a, s);
 }
 
 template <int KH, int KW>
@@ -977,12 +971,6 @@ int launch_convolve_direct(KxkArgs a, hipStream_t s) {
     hipLaunchKernelGGL((convolve_direct_kernel<KH, KW, RB>), dim3((unsigned)xcd_grid(a.n_tiles, a.tiles_x)), dim3(256), 0, s, a);
     XRS_LAUNCH_CHECK();
     return 0;
-}
-
-// XRS_FOCAL_VARIANT=lds forces the LDS-tile kernels for small masks (A/B measurements; default: direct)
-bool prefer_lds() {
-    const char *e = ab_env("XRS_FOCAL_VARIANT");
-    return e && strcmp(e, "lds") == 0;
 }
 
 // Column walkers (kxk_circle*.hip, kxk_box*.hip) for masks that are circles or boxes: -1 if neither.
@@ -1006,31 +994,13 @@ int try_walk_f64(const float *in, float *mean, float *var, float *sd, long rows,
     return rc;
 }
 
-// XRS_FOCAL_VARIANT=strip keeps small circular masks on the register-strip all-statistics kernel (A/B; default: walker)
-bool prefer_strip() {
-    const char *e = ab_env("XRS_FOCAL_VARIANT");
-    return e && (strcmp(e, "strip") == 0 || strcmp(e, "lds") == 0);
-}
-
 template <bool MEAN_ONLY>
 int dispatch_focal(const KxkArgs &a, bool vec, size_t lds, hipStream_t s) {
     // (the register-strip kernels take any width / pitch / base address; `vec` only gates the LDS-tile kernels)
-    if (MEAN_ONLY && !prefer_lds()) {
-        if (a.krows == 3 && a.kcols == 3) return launch_mean_direct<3, 3>(a, s);
-        if (a.krows == 5 && a.kcols == 5) return launch_mean_direct<5, 5>(a, s);
-        // (7x7 would need 256 VGPRs in registers: it stays on the LDS-tile kernel)
-    }
-    if (MEAN_ONLY && vec && a.th == TH_FAST) {
-        if (a.krows == 3 && a.kcols == 3) return launch_mean_fast<3, 3>(a, lds, s);
-        if (a.krows == 5 && a.kcols == 5) return launch_mean_fast<5, 5>(a, lds, s);
-        if (a.krows == 7 && a.kcols == 7) return launch_mean_fast<7, 7>(a, lds, s);
-    }
-    if (!MEAN_ONLY && !prefer_lds()) {
-        if (a.krows == 3 && a.kcols == 3) return launch_stats_direct<3, 3>(a, s);
-        if (a.krows == 5 && a.kcols == 5) return launch_stats_direct<5, 5>(a, s);
-    }
-    // (the unrolled all-statistics bodies need > 170 VGPRs beyond 3x3; the runtime walk needs ~72)
-    if (a.krows == 3 && a.kcols == 3) return launch_focal<3, 3, MEAN_ONLY ? 0 : 1>(a, vec, lds, s);
+    if (a.krows == 3 && a.kcols == 3) return MEAN_ONLY ? launch_mean_direct<3, 3>(a, s) : launch_stats_direct<3, 3>(a, s);
+    if (a.krows == 5 && a.kcols == 5) return MEAN_ONLY ? launch_mean_direct<5, 5>(a, s) : launch_stats_direct<5, 5>(a, s);
+    // (7x7 would need 256 VGPRs in registers: it stays on the LDS-tile kernel)
+    if (MEAN_ONLY && vec && a.th == TH_FAST && a.krows == 7 && a.kcols == 7) return launch_mean_fast<7, 7>(a, lds, s);
     return launch_focal<0, 0, MEAN_ONLY ? 0 : 1>(a, vec, lds, s);
 }
 
@@ -1098,9 +1068,9 @@ int xrs_convolve2d_f32(const float *in_dev, float *out_dev, int64_t rows, int64_
     hipStream_t s = as_stream(stream);
     XRS_HIP(hipMemcpyAsync(work_dev, kernel, (size_t)krows * kcols * sizeof(double), hipMemcpyHostToDevice, s));
     a.weights = static_cast<const double *>(work_dev);
-    if (krows >= 7 && !ab_env("XRS_CONV_TAPS")) {
+    if (krows >= 7) {
         // one weight value on a circle / box (normalised circle_kernel, np.ones / k^2): the wide row walker (wide_impl.h,
-        // float32 on shifted values, guarded).  (Round 1's float64 column walker: experiments/superseded/.)
+        // float32 on shifted values, guarded)
         int rc = -1;
         rc = try_launch_conv_wide_circle(in_dev, out_dev, rows, cols, ld_in, ld_out, kernel, a.weights, krows, kcols, halo_top, halo_bot, s);
         if (rc < 0)
@@ -1111,20 +1081,13 @@ int xrs_convolve2d_f32(const float *in_dev, float *out_dev, int64_t rows, int64_
     }
     a.tiles_x = (cols + TW - 1) / TW;
     a.n_tiles = a.tiles_x * ((rows + a.th - 1) / a.th);
+    if (krows == 3 && kcols == 3) return launch_convolve_direct<3, 3>(a, s);
+    if (krows == 5 && kcols == 5) return launch_convolve_direct<5, 5>(a, s);
     const unsigned grid = (unsigned)xcd_grid(a.n_tiles, XCD_UNIT(XRS_XCD_LDS, a.tiles_x));
     const bool vec = vec_ok(a, 1u);
-#define XRS_CONV(KH, KW)                                                                              \
-    do {                                                                                              \
-        if (int rc_ = vec ? allow_big_lds(&convolve_kernel<KH, KW, true>, lds) : allow_big_lds(&convolve_kernel<KH, KW, false>, lds)) return rc_; \
-        if (vec) hipLaunchKernelGGL((convolve_kernel<KH, KW, true>), dim3(grid), dim3(256), lds, s, a);  \
-        else hipLaunchKernelGGL((convolve_kernel<KH, KW, false>), dim3(grid), dim3(256), lds, s, a);     \
-    } while (0)
-    if (!prefer_lds() && krows == 3 && kcols == 3) return launch_convolve_direct<3, 3>(a, s);
-    if (!prefer_lds() && krows == 5 && kcols == 5) return launch_convolve_direct<5, 5>(a, s);
-    if (krows == 3 && kcols == 3) XRS_CONV(3, 3);
-    else if (krows == 5 && kcols == 5) XRS_CONV(5, 5);
-    else XRS_CONV(0, 0);
-#undef XRS_CONV
+    if (int rc = vec ? allow_big_lds(&convolve_kernel<0, 0, true>, lds) : allow_big_lds(&convolve_kernel<0, 0, false>, lds)) return rc;
+    if (vec) hipLaunchKernelGGL((convolve_kernel<0, 0, true>), dim3(grid), dim3(256), lds, s, a);
+    else hipLaunchKernelGGL((convolve_kernel<0, 0, false>), dim3(grid), dim3(256), lds, s, a);
     XRS_LAUNCH_CHECK();
     return 0;
 }
@@ -1173,11 +1136,9 @@ int xrs_focal_stats_f32_ex(const float *in_dev, float *const *outs_dev, unsigned
     // Large circles / boxes: the float32 walkers of wide_impl.h / ext_impl.h / mom_impl.h.  XRS_FOCAL_EXACT_MOMENTS keeps
     // the float64 column walkers (mean / var / std within ~1 ulp of the reference's float64 accumulators, ~2x the time);
     // XRS_FOCAL_SEQUENTIAL_SUM keeps `sum` on the kernel that adds the taps in the reference's order in float32 (bit-exact
-    // with numba's nansum) instead of rounding the exact sum once.  (`make AB=1`: XRS_FOCAL_GEN=1 selects the first generation
-    // for A/B runs; the second lives in experiments/superseded/.)
+    // with numba's nansum) instead of rounding the exact sum once.
     if (flags & ~(unsigned)(XRS_FOCAL_EXACT_MOMENTS | XRS_FOCAL_SEQUENTIAL_SUM)) return fail("xrs_focal_stats_f32_ex: unknown flag bits 0x%x", flags);
-    const char *gen = ab_env("XRS_FOCAL_GEN");
-    const bool gen1 = (flags & XRS_FOCAL_EXACT_MOMENTS) || (gen && gen[0] == '1');
+    const bool gen1 = (flags & XRS_FOCAL_EXACT_MOMENTS) != 0;
     const bool seq_sum = (flags & XRS_FOCAL_SEQUENTIAL_SUM) != 0;
     const unsigned m_mean = 1u << XRS_STAT_MEAN, m_sum = 1u << XRS_STAT_SUM;
     if (!gen1 && krows == kcols && krows >= 7 && !(stat_mask & ~(m_mean | m_sum)) && !((stat_mask & m_sum) && seq_sum)) {
@@ -1243,7 +1204,7 @@ int xrs_focal_stats_f32_ex(const float *in_dev, float *const *outs_dev, unsigned
             // (rc < 0: neither a circle nor a box of radius 4..12 -- the kernels below)
         }
     }
-    if (stat_mask == (1u << XRS_STAT_MEAN) && krows * kcols >= 49 && !ab_env("XRS_FOCAL_MEAN_RUNS")) {
+    if (stat_mask == (1u << XRS_STAT_MEAN) && krows * kcols >= 49) {
         // circles and boxes, 7x7 .. 25x25: column walker (running float64 sums over centred runs)
         const int rc = try_walk_f64(in_dev, a.out[XRS_STAT_MEAN], nullptr, nullptr, rows, cols, ld_in, ld_out, kernel,
                                     krows, kcols, halo_top, halo_bot, s);
@@ -1301,22 +1262,21 @@ int xrs_focal_stats_f32_ex(const float *in_dev, float *const *outs_dev, unsigned
             return launch_focal<0, 0, 2>(a, vec, lds, s);
         }
     }
-    if (stat_mask == (1u << XRS_STAT_MEAN) && !prefer_lds() && !ab_env("XRS_FOCAL_MEAN_DIRECT") &&
-        pass_has_compile_time_mask(kernel, krows, kcols)) {
+    if (stat_mask == (1u << XRS_STAT_MEAN) && pass_has_compile_time_mask(kernel, krows, kcols)) {
         // circle_kernel(1, 1, 2) / np.ones((3, 3)): the strip kernel of pass.hip without terrain products -- compile-time
-        // mask, shared row sums (XRS_FOCAL_MEAN_DIRECT=1: this file's run-time-mask kernel, A/B runs)
+        // mask, shared row sums
         return xrs_raster_pass_f32(in_dev, nullptr, nullptr, nullptr, nullptr, a.out[XRS_STAT_MEAN], kernel, krows, kcols, work_dev,
                                    rows, cols, ld_in, ld_out, 1.0, 1.0, 0.0, 0.0, halo_top, halo_bot, stream);
     }
     if (stat_mask == (1u << XRS_STAT_MEAN)) return dispatch_focal<true>(a, vec, lds, s);
-    if ((krows == 5 || krows == 7) && krows == kcols && !gen1 && !(seq_sum && a.out[XRS_STAT_SUM]) && !ab_env("XRS_FOCAL_SW_OFF") &&
+    if ((krows == 5 || krows == 7) && krows == kcols && !gen1 && !(seq_sum && a.out[XRS_STAT_SUM]) &&
         (a.out[XRS_STAT_VAR] || a.out[XRS_STAT_STD] || a.out[XRS_STAT_MEAN])) {
         // small circles / boxes with moments among the statistics: everything from one pass of the strip walker (sw_impl.h)
         int rc = try_launch_focal_sw_circle(in_dev, a.out, rows, cols, ld_in, ld_out, kernel, krows, kcols, halo_top, halo_bot, s);
         if (rc < 0) rc = try_launch_focal_sw_box(in_dev, a.out, rows, cols, ld_in, ld_out, kernel, krows, kcols, halo_top, halo_bot, s);
         if (rc >= 0) return rc;
     }
-    if (krows <= 7 && krows == kcols && (krows >= 5 || ab_env("XRS_FOCAL_WALK3")) && !prefer_strip()) {
+    if (krows <= 7 && krows == kcols && krows >= 5) {
         // small circles / boxes (5x5, 7x7): all requested statistics from one column-walker kernel
         const bool f32_stats = a.out[XRS_STAT_SUM] || a.out[XRS_STAT_MAX] || a.out[XRS_STAT_MIN] || a.out[XRS_STAT_RANGE];
         const int rc = f32_stats

@@ -60,9 +60,6 @@ __device__ __forceinline__ int mom_clipped_count(long yo, long x, long y_lo, lon
 // cells outside (a reader turns them into w = 0), divisors = the geometric count of in-raster cells under each window,
 // ONE shift per lane for the whole tile (no re-centring: the number of cells a partial sum has seen is not a compile-time
 // constant here).  The guard is the same, so on steep relief an edge tile is more likely to end in the exact walker.
-#ifndef XRS_MOM_CARRY_ALWAYS
-#define XRS_MOM_CARRY_ALWAYS 1    // the carrying walk's output rows: 1 = always through the lost ring (no branch), 0 = only under NaN rows
-#endif
 // CARRY (interior tiles, solid shapes): nodata carried by the walk itself -- the second walk of a tile whose first, plain walk
 // met a NaN (the scheme of wide_impl.h's carrying walk).  At the head of a step the lanes vote on the cells of the row that has
 // just landed in the ring; a row that holds NaN has them overwritten IN THE RING with `fill`, one finite value per tile, and
@@ -239,9 +236,6 @@ struct MomWalk {
     // NC results per lane to the wave-uniform row address `p` (streaming store, scalar base + 32-bit lane offset: the
     // compiler otherwise keeps a 64-bit lane address per output plane alive across the walk)
     __device__ __forceinline__ void store_row(float *p, stNC v) const {
-#ifdef XRS_FLOOR_NO_STORES                                     // (tools/floor_probe.sh: the walk without its output streams)
-        if (g.rows >= 0) return;
-#endif
         const unsigned lane_b = (unsigned)(NC * 4) * (unsigned)(NANOK ? lane_here() : lane);
         if (NC == 2) { lds_dma_v2f q; q[0] = v[0]; q[1] = v[NC - 1]; st_row_nt(uniform_ptr(p), lane_b, q); }
         else if (NC == 1) st_row_nt(uniform_ptr(p), lane_b, v[0]);
@@ -468,22 +462,11 @@ struct MomWalk {
         // ---- the NV cells under the lane's windows about the lane's shift, lane-local prefix sums, and every distinct
         // half-width once into the ring slots of the output rows that see this row with it: first the values, then their
         // squares.  (The compiler merges the two passes' reads and subtractions.  Forcing a second set of reads with a
-        // memory barrier between the passes -- XRS_MOM_SPLIT_READS -- should need 26 registers less; this compiler then
+        // memory barrier between the passes should need 26 registers less; this compiler then
         // spills 53 instead.)
         asm volatile("" : "+v"(row));                         // (one base register + immediate offsets for the reads)
-#ifdef XRS_FLOOR_NO_ARITH                                      // (tools/floor_probe.sh: the DMA ring and the stores, no reads / sums)
-        if (g.rows < 0)
-#endif
         moment_pass<PHASE, false>(row);
-#ifdef XRS_MOM_SPLIT_READS
-        asm volatile("" ::: "memory");
-#endif
-#ifndef XRS_MOM_T_NOQ
-#ifdef XRS_FLOOR_NO_ARITH
-        if (g.rows < 0)
-#endif
         moment_pass<PHASE, true>(row);
-#endif
 
         if (EDGE) {
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -525,10 +508,11 @@ struct MomWalk {
             out_off += g.ld_out;
             constexpr float inv = 1.0f / (float)C::NTAPS;
             stNC r_sum, r_mean, r_var, r_std;
-            // (wave-uniform) NaN rows under this output row's windows.  (Marked likely -- at 0.1 % nodata it is 97 % of the output
-            // rows -- the block moves in line and the round loop spills 10 registers; out of line it is the block that spills,
-            // the one of the round's last step only: one column at a time there, below)
-            if (NANOK && (XRS_MOM_CARRY_ALWAYS || __builtin_expect(inflight != 0u, 0))) {
+            // The carrying walk takes every output row through the lost ring, with no branch on whether NaN rows lie under its
+            // windows.  (Branching on that, marked likely -- at 0.1 % nodata it is 97 % of the output rows -- the block moves in
+            // line and the round loop spills 10 registers; out of line it is the block that spills, the one of the round's last
+            // step only: one column at a time there, below)
+            if (NANOK) {
                 const unsigned lost_pk = lost_cells();
                 const float dl = fill - c, dl2 = dl * dl;
 #pragma unroll
@@ -607,9 +591,7 @@ struct MomWalk {
         };
         (one(std::integral_constant<int, J>{}), ...);
         c = c_next;
-#ifndef XRS_MOM_T_NONANSTOP
         badm |= __builtin_amdgcn_ballot_w64(c != c);             // a NaN under the round's runs: stop now, not 2R rows later
-#endif
         if constexpr (NANOK) {
             // (the carrying walk has no registers for the two-term history: ONE decaying maximum, x 0.85 per round -- 0.85, 0.72,
             // 0.61, 0.52: never below MomCfg's table either, a little more conservative than the plain walk's)
@@ -633,9 +615,7 @@ struct MomWalk {
         ring_rotate<K, U>(accQ);
         t += U;
         if (HOLE) hk *= HK_DECAY;
-#ifndef XRS_MOM_T_NORECENTRE
         if (!EDGE && !NANOK) recentre(std::make_integer_sequence<int, K>{});
-#endif
     }
 
     // true: every result of the tile is good; false: the caller redoes the tile with the float64 walker
@@ -666,9 +646,6 @@ __device__ __forceinline__ void mom_exact_tile(const MomArgs &a, long x_tile, in
     }
 }
 
-#ifndef XRS_MOM_CARRY
-#define XRS_MOM_CARRY 1           // NaN tiles: the carrying walk before the NaN-aware one-column walker
-#endif
 #ifndef XRS_MOM_WAVES
 #define XRS_MOM_WAVES 2           // workgroups per CU = waves per SIMD
 #endif
@@ -676,7 +653,7 @@ template <int R, typename Shape, int OM>
 __global__ void __launch_bounds__(256, XRS_MOM_WAVES) focal_mom_kernel(const MomArgs a) {
     using C = MomCfg<R, Shape>;
     __shared__ __attribute__((aligned(16))) float lds_rows[4][(C::D + 1) * C::RBF];
-    constexpr bool CARRIES = XRS_MOM_CARRY && OM != 0 && MomWalk<R, Shape, OM, false, true>::NANOK;
+    constexpr bool CARRIES = OM != 0 && MomWalk<R, Shape, OM, false, true>::NANOK;
     __shared__ unsigned nan_row[4][8];                         // per wave: the NaN bitmap of the row being marked
     __shared__ unsigned short lost_ring[4][CARRIES ? C::K * 64 : 1];   // per wave: NaN cells under the windows in flight
     long ty, gx;
@@ -695,18 +672,11 @@ __global__ void __launch_bounds__(256, XRS_MOM_WAVES) focal_mom_kernel(const Mom
         MomWalk<R, Shape, OM, false> w(a, lds_rows[wv], x_tile, y0, y_end, lane);
         if (w.run()) return;
     } else {
-#ifdef XRS_MOM_T_SKIPEDGE
-        return;
-#endif
         // (rim tiles without NaN cells on gentle relief stay on the two-column walk: one fixed shift per lane, geometric counts)
         MomWalk<R, Shape, OM, true> w(a, lds_rows[wv], x_tile, y0, y_end, lane);
         if (w.run()) return;
     }
-#ifdef XRS_MOM_NO_FALLBACK
-    return;
-#endif
     // the fast walk met a non-finite sum or failed its guard.  Inside a nodata region: nothing to walk
-#ifndef XRS_MOM_T_NOALLNAN
     if (walk_tile_all_nan<(C::TW + 2 * R + 63) / 64>(g, x_tile - R, x_tile + C::TW + R, y0 - R, y_end + R, lane)) {
         float *const planes[3] = {a.out_mean, a.out_var, a.out_std};
         if (C::TW == 128 && x_tile + 128 <= g.cols) {
@@ -717,7 +687,6 @@ __global__ void __launch_bounds__(256, XRS_MOM_WAVES) focal_mom_kernel(const Mom
         }
         return;
     }
-#endif
     // NaN cells under a window (scattered nodata, a nodata region's rim): the SAME two-column walk again, this time carrying
     // them (MomWalk<.., CARRY>: ~1.2x a plain walk; the plain walk in front of it stopped at the first round that met a
     // NaN, so a clean raster pays nothing).  Interior tiles of solid shapes with a compile-time plane set.
@@ -727,9 +696,6 @@ __global__ void __launch_bounds__(256, XRS_MOM_WAVES) focal_mom_kernel(const Mom
             w.nanmap = nan_row[wv];
             w.lostring = lost_ring[wv];
             if (w.run()) return;
-#ifdef XRS_MOM_CARRY_ONLY          // (probe builds: what the carrying walk alone costs, and which tiles it hands on -- their outputs stay unwritten)
-            return;
-#endif
         }
     }
     // What is left -- the rim of a nodata region, dense nodata, raster-edge tiles on nodata, +-inf -- is slow work for one wave
@@ -750,16 +716,12 @@ __global__ void __launch_bounds__(256, XRS_MOM_WAVES) focal_mom_kernel(const Mom
     // (Tried: the four waves of the workgroup sharing those exact walks behind a barrier -- a nodata boundary leaves one
     // slow tile per tile row, ~0.8 ms of kernel tail.  It shortened that raster's time by 7 % and cost EVERY raster 5 %:
     // the changed control flow pushed scalar registers of the interior loop into VGPR lanes, 48-56 v_readlane per round
-    // instead of 8.  A kernel argument read only by the NaN-aware walker did the same.  tools/readlanes.sh counts them.)
+    // instead of 8.  A kernel argument read only by the NaN-aware walker did the same.)
     for (int q = 0; q < C::NC; ++q) {
         if (x_tile + 64 * q >= g.cols) break;
-#ifndef XRS_MOM_NO_NANWALK
         MomWalkN<R, Shape, OM> w(a, lds_rows[wv], x_tile + 64 * q, y0, y_end, lane);
         if (w.run()) continue;
-#endif
-#ifndef XRS_MOM_NO_EXACT           // (debug builds: keep what the NaN-aware walker wrote -- tests/mom_boundary_probe.py)
         mom_exact_tile<R, Shape>(a, x_tile, lane, y0, y_end, q, 1);
-#endif
     }
 }
 
@@ -801,15 +763,9 @@ __global__ void __launch_bounds__(256, 2) focal_mom_rescue_kernel(const MomArgs 
         const long y0 = yt0 + (long)band * band_rows;
         const long y_end = y0 + band_rows < yt1 ? y0 + band_rows : yt1;
         if (y0 >= y_end) continue;
-#ifdef XRS_RESCUE_EXACT_ONLY        // (probe builds: which stage of the rescue is responsible for a wrong cell)
-        mom_exact_tile<R, Shape>(a, x_tile, lane, y0, y_end, q, 1);
-        continue;
-#endif
         MomWalkN<R, Shape, OM> w(a, stage[wv], xw, y0, y_end, lane);
-#ifndef XRS_RESCUE_NO_FIX
         w.fix_list = fixes[wv];
         w.fix_cap = RESCUE_FIX;
-#endif
         if (w.run()) {
             if (w.n_fix) {
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -856,7 +812,7 @@ int launch_mom(MomArgs &a, const double *kernel, hipStream_t s) {
     g.n_tiles = g.tiles_x * tiles_y;
     a.groups_x = (g.tiles_x + 3) / 4;
     a.n_groups = a.groups_x * tiles_y;
-    a.rim_first = RimFirst::mode_from_env();
+    a.rim_first = 1;
     const long grid = RimFirst(a.groups_x, tiles_y, a.rim_first).grid();
     if (grid > 0x7fffffffL) return fail("focal moments: raster too large for one launch");
     if (std::is_same<Shape, BoxShape>::value && a.todo) {
@@ -924,9 +880,7 @@ int XRS_MOM_ENTRY(const float *in, float *out_sum, float *out_mean, float *out_v
     a.todo = todo_dev;
     switch (krows / 2) {
 #define XRS_MOM_CASE(RR) case RR: return launch_mom<RR, XRS_MOM_SHAPE>(a, kernel, s);
-#ifndef XRS_MOM_PROBE
         XRS_MOM_CASE(4) XRS_MOM_CASE(5) XRS_MOM_CASE(6) XRS_MOM_CASE(7) XRS_MOM_CASE(8) XRS_MOM_CASE(9) XRS_MOM_CASE(10) XRS_MOM_CASE(11)
-#endif
         XRS_MOM_CASE(12)
 #undef XRS_MOM_CASE
         default: return -1;

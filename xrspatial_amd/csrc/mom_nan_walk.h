@@ -176,7 +176,7 @@ struct MomWalkN {
         // -- the last columns left of a region's rim -- was never "seeded" by its own cells, and this function then put c back
         // to 0 at the head of EVERY round, under sums accumulated about the shift the re-centring had moved to: garbage that
         // no guard sees.  Masked until round 6 because such a tile always held a window that failed and went to the exact
-        // walker as a whole; tests/probes/rescue_debug.py found it the day single windows began to be repaired.)
+        // walker as a whole; it surfaced the day single windows began to be repaired.)
         float s = 0.0f, n = 0.0f, sh = 0.0f, nh = 0.0f;
 #pragma unroll
         for (int r = 0; r < U; ++r) {
@@ -470,9 +470,6 @@ __device__ __forceinline__ void mom_fix_cells(const MomArgs &a, const unsigned s
             const double vr = q / cnt;
             mean = (float)m; var = (float)vr; sd = (float)sqrt(vr);
         }
-#ifdef XRS_RESCUE_MARK             // (probe builds: flagged windows show up as -12345 in the mean plane)
-        mean = -12345.0f;
-#endif
         if (lane == 0) {
             const long off = yo * g.ld_out + x;
             if (a.out_mean) a.out_mean[off] = mean;

@@ -68,9 +68,6 @@ __device__ __forceinline__ void put4(float *p, const float (&v)[4], int n = 4) {
 // CMASK: the window's taps as a compile-time constant (bit ky * KW + kx), 0 = read them from a.mask_rows at run time.
 // With the mask known, the tap walk is straight-line code with no scalar branch per tap row (the circular 5x5 mask of
 // `circle_kernel(1, 1, 2)` -- the bench's -- is instantiated this way).
-#ifndef XRS_PASS_SHARED_ROWS
-#define XRS_PASS_SHARED_ROWS 1
-#endif
 template <int OPS, int KH, int KW, int RB, bool INTERIOR, bool NT, unsigned CMASK = 0u>
 __device__ __forceinline__ void pass_body(const PassArgs &a, long x_tile, long y0, int lane) {
     constexpr int RX = KW / 2, RY = KH / 2, NV = 4 + 2 * RX, NR = RB + KH - 1;
@@ -88,7 +85,7 @@ __device__ __forceinline__ void pass_body(const PassArgs &a, long x_tile, long y
         constexpr bool FINITE = decltype(finite)::value;
         const long y_lo = -(long)a.halo_top, y_hi = a.rows + a.halo_bot;
         const float qnan = nan_f32();
-        // (slope / aspect: Horn sums cell by cell here -- sharing the differences along the strip, terrain.hip's HornRoller,
+        // (slope / aspect: Horn sums cell by cell here -- sharing the differences along the strip (terrain.hip),
         //  needs 40 more VGPRs next to the focal accumulators and costs this kernel an occupancy step: 0.99 vs 0.87 ms)
         constexpr bool HORN = (OPS & (OP_SLOPE | OP_ASPECT)) != 0;
         const SlopeK sk = slope_constants(a.inv8cx, a.inv8cy);
@@ -139,7 +136,7 @@ __device__ __forceinline__ void pass_body(const PassArgs &a, long x_tile, long y
     // products + mean: 1.19 -> 1.37 ms)
     float *fout = a.focal + y0 * a.ld_out + x_tile;
     const int nown = INTERIOR ? 4 : (int)(a.cols - x0 < 4 ? a.cols - x0 : 4);
-    strip_focal_mean<KH, KW, RB, CMASK, XRS_PASS_SHARED_ROWS && !(OPS & OP_ASPECT), OPS == 0, INTERIOR>(
+    strip_focal_mean<KH, KW, RB, CMASK, !(OPS & OP_ASPECT), OPS == 0, INTERIOR>(
         v, a.mask_rows, a.ntaps, a.inv_ntaps, rows_hit, [&](int r, const float (&m)[4]) {
             if (!INTERIOR && y0 + r >= a.rows) return;
             put4<NT>(fout + r * a.ld_out + loff, m, nown);

@@ -169,22 +169,17 @@ template <int K>
 int launch(const CellArgs &q, hipStream_t s) {
     if (q.n <= 0) return 0;
     const bool vec = aligned16(q.a) && aligned16(q.b) && aligned16(q.out) && (Bands<K>::n != 3 || aligned16(q.c));
-    const char *variant = ab_env("XRS_PERCELL_VARIANT");
-    if (vec && !(variant && variant[0] == 'g')) {              // default: one-shot chunks ('g' = grid-stride, for A/B)
+    if (vec) {                                                 // one-shot chunks
         const long n_chunks = ((q.n >> 2) + 1023) / 1024 > 0 ? ((q.n >> 2) + 1023) / 1024 : 1;
         hipLaunchKernelGGL((percell_chunk_kernel<K>), dim3((unsigned)xcd_grid(n_chunks, 1)), dim3(256), 0, s, q, n_chunks);
         XRS_LAUNCH_CHECK();
         return 0;
     }
-    const long work = vec ? ((q.n + 3) >> 2) : q.n;
-    long grid = (work + 255) / 256;
+    long grid = (q.n + 255) / 256;
     const long cap = 256L * 16;            // 256 CUs x 16 workgroups, grid-stride beyond
     if (grid > cap) grid = cap;
     if (grid < 1) grid = 1;
-    if (vec)
-        hipLaunchKernelGGL((percell_kernel<K, true>), dim3((unsigned)grid), dim3(256), 0, s, q);
-    else
-        hipLaunchKernelGGL((percell_kernel<K, false>), dim3((unsigned)grid), dim3(256), 0, s, q);
+    hipLaunchKernelGGL((percell_kernel<K, false>), dim3((unsigned)grid), dim3(256), 0, s, q);
     XRS_LAUNCH_CHECK();
     return 0;
 }

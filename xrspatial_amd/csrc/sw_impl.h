@@ -436,9 +436,7 @@ int XRS_SW_ENTRY(const float *in, float *const *outs, long rows, long cols, long
     if (!any) return 0;
     switch (krows / 2) {
         case 2: return launch_sw<2, XRS_SW_SHAPE, 4>(a, kernel, s);
-#ifndef XRS_SW_NO_R3
         case 3: return launch_sw<3, XRS_SW_SHAPE, 2>(a, kernel, s);
-#endif
         default: return -1;
     }
 }

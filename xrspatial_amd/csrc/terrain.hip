@@ -63,9 +63,6 @@ __device__ __forceinline__ void store_n(OutT *p, const float (&v)[4], int n) {
 #ifndef XRS_STRIP_WX
 #define XRS_STRIP_WX 1
 #endif
-#ifndef XRS_HORN_MODE
-#define XRS_HORN_MODE 0      // 0: Horn sums cell by cell (horn_cell), 1: differences shared along the strip (HornRoller)
-#endif
 
 // ---------------------------------------------------------------- fast path
 // INTERIOR: wave-uniform fact that the wave's whole (RB+2) x 258 input window lies inside the raster
@@ -108,11 +105,8 @@ __device__ __forceinline__ void terrain_strip_body(const TerrainArgs &a, long x_
     }
 
     const float qnan = nan_f32();
-    // slope / aspect: the strip's Horn sums, differences shared between its cells (terrain_cells.h)
+    // slope / aspect: the Horn sums cell by cell (terrain_cells.h)
     constexpr bool HORN = (OPS & (OP_SLOPE | OP_ASPECT)) != 0;
-    const bool horn = HORN && ((a.out[0] && (OPS & OP_SLOPE)) || (a.out[1] && (OPS & OP_ASPECT)));   // wave-uniform
-    HornRoller roll;
-    if (horn && XRS_HORN_MODE == 1) roll.start(&v[0][0], &v[1][0]);
     const SlopeK sk = slope_constants(a.inv8cx, a.inv8cy);
 #pragma unroll
     for (int r = 0; r < RB; ++r) {
@@ -121,7 +115,6 @@ __device__ __forceinline__ void terrain_strip_body(const TerrainArgs &a, long x_
         const bool row_border = !INTERIOR && ((y - 1 < y_lo) || (y + 1 >= y_hi));
         float o_slope[4], o_aspect[4], o_curv[4], o_hill[4];
         Horn hs[4];
-        if (horn && XRS_HORN_MODE == 1) roll.step(&v[r + 2][0], hs);
 #pragma unroll
         for (int o = 0; o < 4; ++o) {
             const long x = x0 + o;
@@ -131,7 +124,7 @@ __device__ __forceinline__ void terrain_strip_body(const TerrainArgs &a, long x_
             q.w = v[r + 1][o];  q.c = v[r + 1][o + 1]; q.e = v[r + 1][o + 2];
             q.sw = v[r + 2][o]; q.s = v[r + 2][o + 1]; q.se = v[r + 2][o + 2];
             // (a.out[i] tests are wave-uniform: the fused instantiation skips absent products)
-            if (HORN && XRS_HORN_MODE == 0) hs[o] = horn_cell(q);
+            if (HORN) hs[o] = horn_cell(q);
             if ((OPS & OP_SLOPE) && a.out[0]) o_slope[o] = border ? qnan : slope_from_horn(hs[o], sk);
             if ((OPS & OP_ASPECT) && a.out[1]) o_aspect[o] = border ? qnan : aspect_from_horn(hs[o]);
             if ((OPS & OP_CURV) && a.out[2]) o_curv[o] = border ? qnan : curvature_cell(q, a.curv_scale);
@@ -157,10 +150,10 @@ __device__ __forceinline__ void terrain_strip_body(const TerrainArgs &a, long x_
     }
 }
 
-// slope / aspect stand-alone, same-box A/B under the row-interleaved tile order (tools/ab_terrain.sh, 16384^2, four rounds,
+// slope / aspect stand-alone, same-box A/B under the row-interleaved tile order (16384^2, four rounds,
 // times relative to hillshade in the same process): Horn sums cell by cell, uncapped (85 VGPRs, 5 waves per SIMD, no
 // scratch) slope 1.07 / aspect 1.12; the same capped at 5 workgroups per CU 1.08 / 1.14; differences shared along the strip
-// (HornRoller: 7 instead of 10 float64 operations per cell, but 104 VGPRs) capped at 5 (96 VGPRs, 13 spilled) 1.09 / 1.16,
+// (7 instead of 10 float64 operations per cell, but 104 VGPRs) capped at 5 (96 VGPRs, 13 spilled) 1.09 / 1.16,
 // uncapped (4 waves per SIMD) 1.10 / 1.20.  Occupancy beats operation count here: cell by cell it is.
 #ifndef XRS_LB_HORN
 #define XRS_LB_HORN 1
@@ -187,47 +180,9 @@ __global__ void __launch_bounds__(256, ((OPS == OP_SLOPE || OPS == OP_ASPECT) &&
     }
 }
 
-// ------------------------------------------------------------- generic path
-template <typename HillT>
-__global__ void __launch_bounds__(256) terrain_cell_kernel(const TerrainArgs a, const int ops) {
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= a.rows * a.cols) return;
-    const long y = idx / a.cols, x = idx - y * a.cols;
-    const long y_lo = -(long)a.halo_top, y_hi = a.rows + a.halo_bot;
-    const bool border = (y - 1 < y_lo) || (y + 1 >= y_hi) || x == 0 || x == a.cols - 1;
-    float r_slope, r_aspect, r_curv, r_hill;
-    r_slope = r_aspect = r_curv = r_hill = nan_f32();
-    if (!border) {
-        const float *p = a.in + y * a.ld_in + x;
-        Nb q;
-        q.nw = p[-a.ld_in - 1]; q.n = p[-a.ld_in]; q.ne = p[-a.ld_in + 1];
-        q.w = p[-1];            q.c = p[0];        q.e = p[1];
-        q.sw = p[a.ld_in - 1];  q.s = p[a.ld_in];  q.se = p[a.ld_in + 1];
-        if (ops & OP_SLOPE) r_slope = slope_cell(q, a.inv8cx, a.inv8cy);
-        if (ops & OP_ASPECT) r_aspect = aspect_cell(q);
-        if (ops & OP_CURV) r_curv = curvature_cell(q, a.curv_scale);
-        if (ops & OP_HILL) r_hill = hillshade_cell(q, a.sin_alt, a.cos_alt, a.cos_az, a.sin_az);
-    }
-    const long off = y * a.ld_out + x;
-    if ((ops & OP_SLOPE) && a.out[0]) static_cast<float *>(a.out[0])[off] = r_slope;
-    if ((ops & OP_ASPECT) && a.out[1]) static_cast<float *>(a.out[1])[off] = r_aspect;
-    if ((ops & OP_CURV) && a.out[2]) static_cast<float *>(a.out[2])[off] = r_curv;
-    if ((ops & OP_HILL) && a.out[3]) static_cast<HillT *>(a.out[3])[off] = (HillT)r_hill;
-}
-
-template <int OPS, typename HillT, int RB>
-int launch_strip_rb(TerrainArgs &a, hipStream_t s);
-
 template <int OPS, typename HillT>
 int launch_strip(TerrainArgs &a, hipStream_t s) {
-    const char *e = ab_env("XRS_TERRAIN_RB");        // A/B knob: rows per wave (default 4)
-    if (e && e[0] == '2') return launch_strip_rb<OPS, HillT, 2>(a, s);
-    if (e && e[0] == '8') return launch_strip_rb<OPS, HillT, 8>(a, s);
-    return launch_strip_rb<OPS, HillT, 4>(a, s);
-}
-
-template <int OPS, typename HillT, int RB>
-int launch_strip_rb(TerrainArgs &a, hipStream_t s) {
+    constexpr int RB = 4;                              // rows per wave
     constexpr int WX = XRS_STRIP_WX, WY = 4 / WX;
     a.tiles_x = (a.cols + 256 * WX - 1) / (256 * WX);
     const long tiles_y = (a.rows + WY * RB - 1) / (WY * RB);
@@ -244,28 +199,14 @@ int terrain_dispatch(TerrainArgs &a, int ops, bool hill_f64, hipStream_t s) {
     if (a.rows < 0 || a.cols < 0 || a.ld_in < a.cols || a.ld_out < a.cols)
         return fail("terrain: bad shape rows=%ld cols=%ld ld_in=%ld ld_out=%ld", a.rows, a.cols, a.ld_in, a.ld_out);
     if (a.halo_top < 0 || a.halo_bot < 0) return fail("terrain: negative halo");
-    // the strip kernels take any width / pitch / base address (dword-aligned 16-byte accesses, ragged last lane);
-    // XRS_TERRAIN_VARIANT=cell forces the one-cell-per-thread kernel (A/B, and the oracle of the ragged path's tests)
-    const char *variant = ab_env("XRS_TERRAIN_VARIANT");
-    const bool fast = !(variant && variant[0] == 'c');
-    if (fast) {
-        switch (ops) {
-            case OP_SLOPE: return launch_strip<OP_SLOPE, float>(a, s);
-            case OP_ASPECT: return launch_strip<OP_ASPECT, float>(a, s);
-            case OP_CURV: return launch_strip<OP_CURV, float>(a, s);
-            case OP_HILL: return hill_f64 ? launch_strip<OP_HILL, double>(a, s) : launch_strip<OP_HILL, float>(a, s);
-            default: return launch_strip<15, float>(a, s);
-        }
+    // the strip kernels take any width / pitch / base address (dword-aligned 16-byte accesses, ragged last lane)
+    switch (ops) {
+        case OP_SLOPE: return launch_strip<OP_SLOPE, float>(a, s);
+        case OP_ASPECT: return launch_strip<OP_ASPECT, float>(a, s);
+        case OP_CURV: return launch_strip<OP_CURV, float>(a, s);
+        case OP_HILL: return hill_f64 ? launch_strip<OP_HILL, double>(a, s) : launch_strip<OP_HILL, float>(a, s);
+        default: return launch_strip<15, float>(a, s);
     }
-    const long n = a.rows * a.cols;
-    const long grid = (n + 255) / 256;
-    if (grid > 0x7fffffffL) return fail("terrain: raster too large for the unaligned path");
-    if (hill_f64)
-        hipLaunchKernelGGL(terrain_cell_kernel<double>, dim3((unsigned)grid), dim3(256), 0, s, a, ops);
-    else
-        hipLaunchKernelGGL(terrain_cell_kernel<float>, dim3((unsigned)grid), dim3(256), 0, s, a, ops);
-    XRS_LAUNCH_CHECK();
-    return 0;
 }
 
 TerrainArgs base_args(const float *in, long rows, long cols, long ld_in, long ld_out, int ht, int hb) {

@@ -18,11 +18,11 @@ struct Nb { float nw, n, ne, w, c, e, sw, s, se; };
 // float64): sums of float32 cells are exact there, for any data.  (An all-float32 "differences first + TwoSum" form is
 // only exact while neighbouring cells are within a factor 2 of each other, costs as many issue slots and measured no
 // faster: slope 0.43 vs 0.40 ms, profiles/r02.)  Differences first: 10 float64 operations per cell
-// and no float64 multiplies (a strip CAN share the differences between its cells -- HornRoller below, 7 per cell -- but the
+// and no float64 multiplies (a strip CAN share the differences between its cells -- 7 operations per cell -- but the
 // registers that takes cost more than the operations save: terrain.hip):
 //   gx = (ne + 2e + se) - (nw + 2w + sw) = (ne - nw) + 2 (e - w) + (se - sw)
 //   gy = (nw + 2n + ne) - (sw + 2s + se) = (nw - sw) + 2 (n - s) + (ne - se)
-// Every path (strip, fused pass, cell-by-cell) evaluates exactly these operations in this order.
+// Every path (strip, fused pass) evaluates exactly these operations in this order.
 struct Horn { double gx, gy; };
 
 __device__ __forceinline__ Horn horn_cell(const Nb &q) {
@@ -33,37 +33,6 @@ __device__ __forceinline__ Horn horn_cell(const Nb &q) {
     r.gy = fma(2.0, g1, g0) + g2;
     return r;
 }
-
-// The Horn sums of a strip, one output row of 4 cells at a time, from the rows of the strip's registers (`row` points at
-// the cell one column left of the lane's first output cell): the float64 images of the last two rows and their
-// east - west differences roll along, so a row costs 6 conversions + 4 + 6 + 16 float64 operations (7 operations and
-// 1.5-2.25 conversions per cell) and 20 live doubles -- computing the whole block up front cost 20-70 more VGPRs and an
-// occupancy step in every kernel that uses it.
-struct HornRoller {
-    double dn[6], dc[6], hn[4], hc[4];
-    __device__ __forceinline__ void start(const float *north, const float *centre) {
-#pragma unroll
-        for (int i = 0; i < 6; ++i) { dn[i] = (double)north[i]; dc[i] = (double)centre[i]; }
-#pragma unroll
-        for (int o = 0; o < 4; ++o) { hn[o] = dn[o + 2] - dn[o]; hc[o] = dc[o + 2] - dc[o]; }
-    }
-    // `south`: the row below the output row; afterwards the roller stands one row further down
-    __device__ __forceinline__ void step(const float *south, Horn (&out)[4]) {
-        double ds[6], hs[4], g[6];
-#pragma unroll
-        for (int i = 0; i < 6; ++i) { ds[i] = (double)south[i]; g[i] = dn[i] - ds[i]; }
-#pragma unroll
-        for (int o = 0; o < 4; ++o) {
-            hs[o] = ds[o + 2] - ds[o];
-            out[o].gx = fma(2.0, hc[o], hn[o]) + hs[o];
-            out[o].gy = fma(2.0, g[o + 1], g[o]) + g[o + 2];
-        }
-#pragma unroll
-        for (int i = 0; i < 6; ++i) { dn[i] = dc[i]; dc[i] = ds[i]; }
-#pragma unroll
-        for (int o = 0; o < 4; ++o) { hn[o] = hc[o]; hc[o] = hs[o]; }
-    }
-};
 
 // atan(z) for 0 <= z <= 1, float32: z + z t p(t), t = z^2, p of degree 7 fitted to (atan(z)/z - 1)/t on [0, 1]
 // (8.3e-8 relative in float32 evaluation, checked against float64 on 2e6 points)
@@ -136,10 +105,6 @@ __device__ __forceinline__ float slope_from_horn(const Horn &g, const SlopeK &k)
     return steep ? 90.0f - r : r;
 }
 
-__device__ __forceinline__ float slope_cell(const Nb &q, double inv8cx, double inv8cy) {
-    return slope_from_horn(horn_cell(q), slope_constants(inv8cx, inv8cy));
-}
-
 // aspect.py:66-88: compass = 90 - atan2(dy, -dx) wrapped to [0, 360) == atan2(-dx, dy) wrapped, with dx = gx / 8 and
 // dy = -gy / 8: the arc tangent does not see the common factor, and evaluating it this way keeps full relative accuracy
 // near 0 degrees.  Flat cells (both sums zero; a float64 sum of float32 cells that is not zero is at least 2^-149, which
@@ -179,8 +144,6 @@ __device__ __forceinline__ float aspect_from_horn(const Horn &g) {
     r = __builtin_isunordered(fx, fy) ? nan_f32() : r;       // (fmax / fmin skip a NaN operand)
     return (fx == 0.0f && fy == 0.0f) ? -1.0f : r;
 }
-
-__device__ __forceinline__ float aspect_cell(const Nb &q) { return aspect_from_horn(horn_cell(q)); }
 
 __device__ __forceinline__ float curvature_cell(const Nb &q, double scale) {
 #pragma clang fp contract(off)   // every instantiation (stand-alone, fused, edge path) rounds identically

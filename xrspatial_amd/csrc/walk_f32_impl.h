@@ -1,5 +1,5 @@
 // Float32 statistics (row-major sum, max, min, range) of focal_stats / focal.apply through the column walker of
-// circle_walk.h, for one mask shape (XRS_WALK_SHAPE) and radius 1..12 cells.  For radius <= 3 the float64 moments ride
+// circle_walk.h, for one mask shape (XRS_WALK_SHAPE) and radius 2..12 cells.  For radius <= 3 the float64 moments ride
 // along in the same kernel (one read of the raster for all seven statistics).  The tap-by-tap walk of kxk.hip this
 // replaces spends 6 VALU + 6 SALU instructions per tap on a 25x25 mask (profiles/r01/pmc_focal25_sum.json).
 // Included by kxk_circle.hip and kxk_box.hip, which define XRS_WALK_SHAPE / XRS_WALK_KERNEL / XRS_WALK_ENTRY.
@@ -55,7 +55,6 @@ int XRS_WALK_ENTRY(const float *in, float *out_sum, float *out_max, float *out_m
     g.halo_top = halo_top; g.halo_bot = halo_bot;
     const WalkOuts o = {out_sum, out_max, out_min, out_range, out_mean, out_var, out_std};
     switch (krows / 2) {
-        case 1: return dispatch<1>(g, o, kernel, moments, s);
         case 2: return dispatch<2>(g, o, kernel, moments, s);
         case 3: return dispatch<3>(g, o, kernel, moments, s);
         case 4: return dispatch<4>(g, o, kernel, moments, s);

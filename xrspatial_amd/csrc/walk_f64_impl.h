@@ -1,5 +1,5 @@
 // Float64 statistics (mean, var, std) of focal_stats / focal.apply through the column walker of circle_walk.h, for
-// one mask shape (XRS_WALK_SHAPE) and radius 1..12 cells.  Included by kxk_circle64.hip and kxk_box64.hip.
+// one mask shape (XRS_WALK_SHAPE) and radius 2..12 cells.  Included by kxk_circle64.hip and kxk_box64.hip.
 #include "circle_walk.h"
 
 using namespace xrs;
@@ -40,7 +40,6 @@ int XRS_WALK_ENTRY(const float *in, float *out_mean, float *out_var, float *out_
     g.halo_top = halo_top; g.halo_bot = halo_bot;
     const WalkOuts o = {nullptr, nullptr, nullptr, nullptr, out_mean, out_var, out_std};
     switch (krows / 2) {
-        case 1: return launch64<1>(g, o, kernel, s);
         case 2: return launch64<2>(g, o, kernel, s);
         case 3: return launch64<3>(g, o, kernel, s);
         case 4: return launch64<4>(g, o, kernel, s);

@@ -68,12 +68,6 @@ using namespace xrs;
 
 namespace {
 
-#ifndef XRS_WIDE_NO_FALLBACK
-#define XRS_WIDE_NO_FALLBACK 0
-#endif
-#ifndef XRS_WIDE_CARRY
-#define XRS_WIDE_CARRY 1          // NaN tiles: the carrying walk (below) before the NaN-aware walker of mom_nan_walk.h
-#endif
 struct WideArgs {
     WalkGeom g;                   // in, rows, cols, ld_in, ld_out, halo_top, halo_bot (tiles_x / n_tiles: wave tiles)
     float *out;                   // the mean, the window sum, or the convolution (template parameter of the kernel)
@@ -103,19 +97,16 @@ struct WideCfg {
     static constexpr int STG = TW + 64;                    // staged cells per row (TW + 2*HL used; every lane writes one halo slot)
     static_assert(2 * HL <= 64, "the halo cells are loaded by one lane each");
     static constexpr int NTAPS = shape_taps<Shape>(R);
-#ifndef XRS_WIDE_SLIDE
-#define XRS_WIDE_SLIDE 1
-#endif
     // np.ones boxes: every row of the window has the same half-width, so the window sum SLIDES down the raster -- V -= H(row
     // that left), V += H(entering row) -- with the ring holding the last row sums H instead of 2R+1 partial window sums: 3
     // ring operations per row and column instead of 2R+1.  That ring is not rotated (its slots change once per row, a rotation
     // would be 2R+1 moves per round, and so would the register copies at the end of a switch over the round's position in
     // it -- both measured): it has KR = a whole number of rounds >= 2R+1 slots, the loop body is all KR / U rounds in a straight
     // line, and a full tile walks a multiple of KR input rows.  V is re-summed from the ring once per KR rows, so the
-    // recurrence rounds at most 2 KR times between two exact states.  Same box, same run (tools/ab_wide.sh): 25x25 mean
+    // recurrence rounds at most 2 KR times between two exact states.  Same box, same run: 25x25 mean
     // 0.55 -> 0.465 ms, uniform-weight 25x25 convolution 0.51 -> 0.465; 15x15 the same either way, 11x11 5 % slower (their
     // ring was 15 / 11 additions to begin with): radius >= 10 only.
-    static constexpr bool SLIDE = XRS_WIDE_SLIDE && R >= 10 && std::is_same<Shape, BoxShape>::value;
+    static constexpr bool SLIDE = R >= 10 && std::is_same<Shape, BoxShape>::value;
 #ifndef XRS_WALK_U
 #define XRS_WALK_U 5
 #endif
@@ -638,9 +629,6 @@ struct WideWalk {
                 stNC rq;
 #pragma unroll
                 for (int o = 0; o < NC; ++o) rq[o] = res[o];
-#ifdef XRS_FLOOR_NO_STORES                                     // (tools/floor_probe.sh: the walk without its output stream)
-                if (g.rows < 0)
-#endif
                 if constexpr (NC == 2) st_row_nt(out_row, 8u * (unsigned)lane, rq);
                 else __builtin_nontemporal_store(rq, reinterpret_cast<stNC *>(out_row + NC * lane));
                 out_row += g.ld_out;
@@ -746,7 +734,7 @@ __global__ void __launch_bounds__(256, XRS_WIDE_WAVES) focal_wide_kernel(const W
         w.wgt = (float)a.wgt;
         ok = w.run();
     }
-    if (ok || XRS_WIDE_NO_FALLBACK) return;
+    if (ok) return;
     constexpr bool SUM = MODE == WIDE_SUM;
     // inside a nodata region (every cell the tile sees is NaN): mean NaN, sum 0, convolution NaN -- nothing to walk
     if (walk_tile_all_nan<(C::TW + 2 * R + 63) / 64>(g, x_tile - R, x_tile + C::TW + R, y0 - R, y_end + R, lane)) {
@@ -759,7 +747,7 @@ __global__ void __launch_bounds__(256, XRS_WIDE_WAVES) focal_wide_kernel(const W
     // vote on the staged cells, in-ring repair, lost ring in LDS -- ~1.3x a plain walk).  The plain walk in front of it stopped
     // at the first round that met a NaN, so a clean raster never pays for any of this.  +-inf, dense nodata, windows with fewer
     // than half their cells and ill-conditioned sums still fail here and go on to the walkers below.
-    if constexpr (MODE != WIDE_CONV && !shape_has_hole<Shape>(R) && XRS_WIDE_CARRY) {
+    if constexpr (MODE != WIDE_CONV && !shape_has_hole<Shape>(R)) {
         bool ok2;
         if (interior) {
             WideWalk<R, Shape, false, MODE, true> w(g, a.out, lds_rows[wv], x_tile, y0, y_end, lane);
@@ -803,12 +791,10 @@ __global__ void __launch_bounds__(256, XRS_WIDE_WAVES) focal_wide_kernel(const W
     ma.out_sum = SUM ? a.out : nullptr; ma.out_mean = SUM ? nullptr : a.out; ma.out_var = nullptr; ma.out_std = nullptr;
     for (int q = 0; q < C::NC; ++q) {
         if (x_tile + 64 * q >= g.cols) break;
-#ifndef XRS_WIDE_NO_NANWALK
         {
             MomWalkN<R, Shape, SUM ? MOM_SUM : MOM_MEAN> w(ma, lds_rows[wv], x_tile + 64 * q, y0, y_end, lane);
             if (w.run()) continue;
         }
-#endif
         if (!SUM) walk_columns<R, Shape, false, false, false, true, false>(g, o, x_tile + 64 * q, lane, y0, y_end);
         else walk_columns<R, Shape, true, true, false, false, false>(g, o, x_tile + 64 * q, lane, y0, y_end);
     }
@@ -893,7 +879,7 @@ int launch_wide(WideArgs &a, float *out_mean, float *out_sum, hipStream_t s) {
     g.n_tiles = g.tiles_x * tiles_y;
     a.groups_x = (g.tiles_x + 3) / 4;
     a.n_groups = a.groups_x * tiles_y;
-    a.rim_first = RimFirst::mode_from_env();
+    a.rim_first = 1;
     const long grid = RimFirst(a.groups_x, tiles_y, a.rim_first).grid();
     if (grid > 0x7fffffffL) return fail("focal mean: raster too large for one launch");
     a.rescue = mom_rescue_slot();
@@ -935,7 +921,7 @@ int launch_wide_conv(WideArgs &a, float *out, const double *kernel, const double
     a.n_groups = a.groups_x * tiles_y;
     a.weights = weights_dev;
     a.out = out;
-    a.rim_first = RimFirst::mode_from_env();
+    a.rim_first = 1;
     const long grid = RimFirst(a.groups_x, tiles_y, a.rim_first).grid();
     if (grid > 0x7fffffffL) return fail("convolve_2d: raster too large for one launch");
     hipLaunchKernelGGL((focal_wide_kernel<R, Shape, WIDE_CONV>), dim3((unsigned)grid), dim3(256), 0, s, a);
@@ -947,10 +933,8 @@ int launch_wide_conv(WideArgs &a, float *out, const double *kernel, const double
 int dispatch_wide_conv(WideArgs &a, float *out, const double *kernel, const double *weights_dev, int r, hipStream_t s) {
     switch (r) {
 #define XRS_WIDE_CASE(RR) case RR: return launch_wide_conv<RR, XRS_WIDE_SHAPE>(a, out, kernel, weights_dev, s);
-#ifndef XRS_WIDE_PROBE
         XRS_WIDE_CASE(3) XRS_WIDE_CASE(4) XRS_WIDE_CASE(5) XRS_WIDE_CASE(6) XRS_WIDE_CASE(7) XRS_WIDE_CASE(8)
         XRS_WIDE_CASE(9) XRS_WIDE_CASE(10) XRS_WIDE_CASE(11)
-#endif
         XRS_WIDE_CASE(12)
 #undef XRS_WIDE_CASE
         default: return -1;
@@ -960,10 +944,8 @@ int dispatch_wide_conv(WideArgs &a, float *out, const double *kernel, const doub
 int dispatch_wide(WideArgs &a, float *out_mean, float *out_sum, const double *kernel, int r, hipStream_t s) {
     switch (r) {
 #define XRS_WIDE_CASE(RR) case RR: return is_shape<RR, XRS_WIDE_SHAPE>(kernel) ? launch_wide<RR, XRS_WIDE_SHAPE>(a, out_mean, out_sum, s) : -1;
-#ifndef XRS_WIDE_PROBE
         XRS_WIDE_CASE(3) XRS_WIDE_CASE(4) XRS_WIDE_CASE(5) XRS_WIDE_CASE(6) XRS_WIDE_CASE(7) XRS_WIDE_CASE(8)
         XRS_WIDE_CASE(9) XRS_WIDE_CASE(10) XRS_WIDE_CASE(11)
-#endif
         XRS_WIDE_CASE(12)
 #undef XRS_WIDE_CASE
         default: return -1;

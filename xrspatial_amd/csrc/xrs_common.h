@@ -41,14 +41,6 @@ inline int fail(const char *fmt, ...) {
                                __FILE__, __LINE__);                                    \
     } while (0)
 
-// A/B switches (XRS_FOCAL_GEN, XRS_CONV_GEN, XRS_RIM_FIRST ...) exist only in `make AB=1` builds: the default library
-// reads no environment variable on a launch path -- ab_env() is a constant there and every branch behind it folds away.
-#ifdef XRS_AB
-inline const char *ab_env(const char *name) { return getenv(name); }
-#else
-constexpr const char *ab_env(const char *) { return nullptr; }
-#endif
-
 // Run-time options of the library (xrs_set_option / xrs_get_option, include/xrs_hip.h): process-wide, relaxed atomics.
 int option_value(int key);
 
@@ -116,69 +108,38 @@ __device__ __forceinline__ xrs_f4u load_f4u(const float *p) { return *reinterpre
 // zonal reductions).  On a 1 GiB + 1 GiB copy on this chip nt loads + nt stores measured 6 290 GB/s against 5 870 with
 // the default policy (experiments/copy_sweep.hip); ndvi / evi / savi gain 4-5 %.  NOT for the stencil kernels' input:
 // their halo rows and columns are re-read by neighbouring strips out of L2, and streaming loads cost them 4-35 %
-// (profiles/r01/nt_ab_r01.log).  XRS_NT=0 builds the default-policy library for A/B runs.
-#ifndef XRS_NT
-#define XRS_NT 1
-#endif
+// (profiles/r01/nt_ab_r01.log).
 typedef float xrs_v4f __attribute__((ext_vector_type(4)));
 typedef float xrs_v4fu __attribute__((ext_vector_type(4), aligned(4)));
 typedef int xrs_v4i __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float4 ldg_stream(const float4 *p) {
-#if XRS_NT
     const xrs_v4f v = __builtin_nontemporal_load(reinterpret_cast<const xrs_v4f *>(p));
     return make_float4(v.x, v.y, v.z, v.w);
-#else
-    return *p;
-#endif
 }
 __device__ __forceinline__ int4 ldg_stream(const int4 *p) {
-#if XRS_NT
     const xrs_v4i v = __builtin_nontemporal_load(reinterpret_cast<const xrs_v4i *>(p));
     return make_int4(v.x, v.y, v.z, v.w);
-#else
-    return *p;
-#endif
 }
 __device__ __forceinline__ void stg_stream(float4 *p, const float4 v) {
-#if XRS_NT
     xrs_v4f q; q.x = v.x; q.y = v.y; q.z = v.z; q.w = v.w;
     __builtin_nontemporal_store(q, reinterpret_cast<xrs_v4f *>(p));
-#else
-    *p = v;
-#endif
 }
 __device__ __forceinline__ xrs_f4u load_f4u_stream(const float *p) {       // dword-aligned 16 bytes
-#if XRS_NT
     const xrs_v4fu v = __builtin_nontemporal_load(reinterpret_cast<const xrs_v4fu *>(p));
     xrs_f4u r; r.x = v.x; r.y = v.y; r.z = v.z; r.w = v.w;
     return r;
-#else
-    return load_f4u(p);
-#endif
 }
 // Results are written once and not read again by the launch that produces them: streaming ("nt") stores.  Same-box A/B
 // (profiles/r01/ntst_ab_r01.log): hillshade 0.386 -> 0.366 ms, slope 0.422 -> 0.400, curvature 0.388 -> 0.361,
-// 5x5 convolve 0.556 -> 0.438, four terrain products 1.147 -> 1.070.  XRS_NT_STENCIL_STORES=0: default policy.
-#ifndef XRS_NT_STENCIL_STORES
-#define XRS_NT_STENCIL_STORES 1
-#endif
+// 5x5 convolve 0.556 -> 0.438, four terrain products 1.147 -> 1.070.
 typedef double xrs_v2du_st __attribute__((ext_vector_type(2), aligned(8)));
 template <typename T>
 __device__ __forceinline__ void st_stream(T *p, const T v) {          // one scalar result per lane
-#if XRS_NT_STENCIL_STORES
     __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
 }
 __device__ __forceinline__ void store_d2u(double *p, double x, double y) {    // two doubles at 8-byte alignment
-#if XRS_NT_STENCIL_STORES
     xrs_v2du_st q; q.x = x; q.y = y;
     __builtin_nontemporal_store(q, reinterpret_cast<xrs_v2du_st *>(p));
-#else
-    xrs_d2u q; q.x = x; q.y = y;
-    *reinterpret_cast<xrs_d2u *>(p) = q;
-#endif
 }
 // A wave's 256 adjacent float64 results (4 per lane, lane l owns columns 4l .. 4l+3) as TWO store instructions that
 // each write 1 KiB of consecutive bytes: lane pairs are transposed through ds_bpermute first.  Every lane storing its own
@@ -208,13 +169,8 @@ __device__ __forceinline__ void store_wave_row_f4_as_d(double *row, int lane, fl
 }
 typedef float xrs_v4fu_st __attribute__((ext_vector_type(4), aligned(4)));
 __device__ __forceinline__ void store_f4u(float *p, float x, float y, float z, float w) {
-#if XRS_NT_STENCIL_STORES
     xrs_v4fu_st q; q.x = x; q.y = y; q.z = z; q.w = w;
     __builtin_nontemporal_store(q, reinterpret_cast<xrs_v4fu_st *>(p));
-#else
-    xrs_f4u q; q.x = x; q.y = y; q.z = z; q.w = w;
-    *reinterpret_cast<xrs_f4u *>(p) = q;
-#endif
 }
 
 // kxk_runs.hip: prefix-sum focal mean for large run-structured masks.  0 = launched, -1 = mask not

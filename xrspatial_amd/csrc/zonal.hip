@@ -124,10 +124,11 @@ struct Acc {
     }
 };
 
-// NT threads per workgroup: 256, or 1024 when the zone table leaves room for only ONE workgroup per CU (more than 64 KiB of
-// LDS: 2 300+ zones) -- 16 waves then share the table instead of 4 (5 000 zones: 1.51 -> 1.36 ms; the rest is the flush of every workgroup's table with device atomics)
+// NT threads per workgroup (the launch uses 1024): 16 waves share one zone table instead of 4 -- with room for only ONE
+// workgroup per CU (more than 64 KiB of LDS: 2 300+ zones) that measured 1.51 -> 1.36 ms for 5 000 zones against 256 threads
+// (the rest is the flush of every workgroup's table with device atomics)
 // (1024-thread workgroups: 8 waves per SIMD = 64 registers, so that TWO workgroups fit a CU when their tables do)
-template <typename VT, bool LDS, bool VEC, int NT = 256, int SLOTS = (NT == 1024 ? 2 : 4)>
+template <typename VT, bool LDS, bool VEC, int NT, int SLOTS = (NT == 1024 ? 2 : 4)>
 __global__ void __launch_bounds__(NT, NT == 1024 && sizeof(VT) == 4 && SLOTS == 2 ? 8 : 1) zonal_kernel(const ZonalArgs<VT> a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     Acc<VT, LDS> acc;
@@ -374,44 +375,33 @@ int zonal_partials(const int32_t *zone_idx_dev, const VT *values_dev, int64_t n,
         // CU's limit) and 512 chunks cover the chip; larger tables: one per CU, 256 chunks.  Measured on 16384^2, 1000 zones
         // (profiles/r03): 256-thread workgroups x 2048 chunks 0.417 ms blocky / 0.469 scattered; 1024 x 512: 0.339 / 0.398 --
         // a quarter of the tables to initialise and flush, and the flushes (rotated start) queue on fewer addresses.
-        // XRS_ZONAL_NT=256 / XRS_ZONAL_CHUNKS=n: the round-2 geometry, for A/B runs.
         const bool big = smem > 64 * 1024;                        // one workgroup per CU
-        bool wide = true;
-        if (const char *e = ab_env("XRS_ZONAL_NT")) wide = atoi(e) != 256;
-        const int nt = (big || wide) ? 1024 : 256;
-        long grid = ((vec ? (n + 3) / 4 : n) + nt - 1) / nt;
-        long cap = big ? 256L : wide ? 512L : 256L * 8;
-        if (const char *e = ab_env("XRS_ZONAL_CHUNKS")) cap = atol(e) > 0 ? atol(e) : cap;
+        long grid = ((vec ? (n + 3) / 4 : n) + 1023) / 1024;
+        const long cap = big ? 256L : 512L;
         if (grid > cap) grid = cap;
         if (n / grid >= (1L << 32)) grid = n / ((1L << 32) - 1) + 1;  // a u32 per-workgroup count cannot overflow
         grid = xcd_grid(grid, 1);                                 // multiple of 8: chunk <-> XCD mapping is a bijection
-        if (nt == 1024) {
-            // once per process and device (idempotent; a race only repeats the call).  Round 3: issued on EVERY call it cost
-            // ~1 ms of the 1.37 ms a 5000-zone reduction of a 16384^2 raster took -- the call synchronises.
-            static thread_local unsigned long long attr_done = 0, attr_big = 0;          // bit d: device d
-            int dev = 0;
-            XRS_HIP(hipGetDevice(&dev));
-            if (dev < 0 || dev >= 64 || !(attr_done >> dev & 1)) {
-                XRS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&zonal_kernel<VT, true, true, 1024>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cap));
-                XRS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&zonal_kernel<VT, true, false, 1024>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cap));
-                if (dev >= 0 && dev < 64) attr_done |= 1ull << dev;
-            }
-            static const int big_slots = ab_env("XRS_ZONAL_BIG_SLOTS") ? atoi(ab_env("XRS_ZONAL_BIG_SLOTS")) : 4;
-            if (big && vec && big_slots == 4) {
-                if (dev < 0 || dev >= 64 || !(attr_big >> dev & 1)) {
-                    XRS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&zonal_kernel<VT, true, true, 1024, 4>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cap));
-                    if (dev >= 0 && dev < 64) attr_big |= 1ull << dev;
-                }
-                hipLaunchKernelGGL((zonal_kernel<VT, true, true, 1024, 4>), dim3((unsigned)grid), dim3(1024), smem, s, a);
-            } else if (vec) hipLaunchKernelGGL((zonal_kernel<VT, true, true, 1024>), dim3((unsigned)grid), dim3(1024), smem, s, a);
-            else hipLaunchKernelGGL((zonal_kernel<VT, true, false, 1024>), dim3((unsigned)grid), dim3(1024), smem, s, a);
-        } else {
-            if (vec) hipLaunchKernelGGL((zonal_kernel<VT, true, true>), dim3((unsigned)grid), dim3(256), smem, s, a);
-            else hipLaunchKernelGGL((zonal_kernel<VT, true, false>), dim3((unsigned)grid), dim3(256), smem, s, a);
+        // once per process and device (idempotent; a race only repeats the call).  Round 3: issued on EVERY call it cost
+        // ~1 ms of the 1.37 ms a 5000-zone reduction of a 16384^2 raster took -- the call synchronises.
+        static thread_local unsigned long long attr_done = 0, attr_big = 0;          // bit d: device d
+        int dev = 0;
+        XRS_HIP(hipGetDevice(&dev));
+        if (dev < 0 || dev >= 64 || !(attr_done >> dev & 1)) {
+            XRS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&zonal_kernel<VT, true, true, 1024>),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cap));
+            XRS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&zonal_kernel<VT, true, false, 1024>),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cap));
+            if (dev >= 0 && dev < 64) attr_done |= 1ull << dev;
         }
+        if (big && vec) {
+            if (dev < 0 || dev >= 64 || !(attr_big >> dev & 1)) {
+                XRS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&zonal_kernel<VT, true, true, 1024, 4>),
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cap));
+                if (dev >= 0 && dev < 64) attr_big |= 1ull << dev;
+            }
+            hipLaunchKernelGGL((zonal_kernel<VT, true, true, 1024, 4>), dim3((unsigned)grid), dim3(1024), smem, s, a);
+        } else if (vec) hipLaunchKernelGGL((zonal_kernel<VT, true, true, 1024>), dim3((unsigned)grid), dim3(1024), smem, s, a);
+        else hipLaunchKernelGGL((zonal_kernel<VT, true, false, 1024>), dim3((unsigned)grid), dim3(1024), smem, s, a);
     }
     XRS_LAUNCH_CHECK();
     return 0;

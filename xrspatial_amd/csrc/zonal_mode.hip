@@ -341,17 +341,12 @@ __global__ void __launch_bounds__(CHUNK_THREADS) scatter_part_kernel(const K *__
                                                                     const Hdr *__restrict__ hdr, unsigned *__restrict__ part_cursor,
                                                                     K *__restrict__ parted) {
     if (DIRECT && !hdr->n_direct) return;
-#ifndef XRS_MODE_NO_XCD_BANDS
     // chunks in contiguous bands per XCD (block b runs on XCD b % 8): the ~64-128 chunks of a zone then write their 16-64 byte
     // runs of every part through ONE L2, which merges them into whole lines before they leave (dealt round-robin, eight L2s
     // each held a slice of every line)
     const long chunk_l = xcd_tile(blockIdx.x, hdr->n_chunks, 0);
     if (chunk_l < 0) return;
     const unsigned chunk = (unsigned)chunk_l;
-#else
-    if (blockIdx.x >= hdr->n_chunks) return;
-    const unsigned chunk = blockIdx.x;
-#endif
     __shared__ unsigned hist[DIRECT ? 1 : (1 << LDS_B)];
     const int z = chunk_zone[chunk];
     const int B = zone_B[z];
@@ -403,7 +398,7 @@ __global__ void __launch_bounds__(CHUNK_THREADS) scatter_part_kernel(const K *__
 // of the result) if taken one by one.  So a workgroup owns a CONTIGUOUS range of parts, reads their descriptors 256 at a time
 // into LDS and keeps the first keys of the next TWO parts in flight while it counts one.  (Contiguous ranges also spread the
 // heavy parts of a categorical raster -- the same few offsets in every zone's 2^B parts -- over all workgroups.)
-// What the pass costs (32768^2, 10^6 parts, tools/zm_variants.sh): its structure without any table 0.2 ms; one returning LDS
+// What the pass costs (32768^2, 10^6 parts): its structure without any table 0.2 ms; one returning LDS
 // add per key 1.85 ms; every key finding its own slot by compare-and-swap 8 ms -- whatever the table size (2048 / 4096 / 8192
 // slots: 8.0 / 7.0 / 11.0), the prefetch depth or the number of adds behind the swap: the probing loop runs until the wave's
 // unluckiest key has walked its cluster.  Hence the sieve in front of it (7.0 ms): two passes, below.

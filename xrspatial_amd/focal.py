@@ -33,7 +33,6 @@ _FLAG_EXACT_MOMENTS, _FLAG_SEQUENTIAL_SUM = 1, 2
 
 
 def _focal_flags():
-    import os
     moments = options.get('moments') or os.environ.get('XRS_FOCAL_MOMENTS') or 'fast'
     sums = options.get('sum') or os.environ.get('XRS_FOCAL_SUM') or 'rounded'
     if moments not in ('fast', 'exact'):
@@ -135,8 +134,6 @@ def _window_workspace(k, rows=0, cols=0):
     # walks hand on -- the rim of a nodata region, dense nodata -- in a work-list inside this block (csrc/mom_impl.h:
     # focal_mom_rescue_kernel, csrc/wide_impl.h: focal_wide_rescue_kernel)
     walked = k.shape[0] == k.shape[1] and 7 <= k.shape[0] <= 25 and k.shape[0] % 2 == 1
-    if os.environ.get("XRS_MOM_RESCUE") == "0":            # (A/B: no work-list, slow tiles are walked in place as before round 6)
-        walked = bool((k == 1.0).all())
     if not (big or walked):
         return None
     return DeviceArray((int(_lib.load().xrs_focal_workspace_bytes(int(rows), int(cols), k.shape[0], k.shape[1])),), np.uint8)
