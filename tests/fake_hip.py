@@ -3,7 +3,7 @@
 `install(monkeypatch)` replaces `xrspatial_amd._lib.call / load / require_device` so that "device" pointers are host
 addresses, copies are memmoves and every stencil entry point is answered by the CPU oracle under the C ABI's own
 row-range / halo contract (a call sees `halo_top` rows above and `halo_bot` rows below the rows it owns and nothing
-else).  That lets the `-m "not gpu"` suite drive the HOST logic of xrspatial_amd.sharded for real -- transports, halo
+else); classify's bin and membership passes are answered by tests/classify_oracle.py.  That lets the `-m "not gpu"` suite drive the HOST logic of xrspatial_amd.sharded for real -- transports, halo
 bookkeeping, chaining, the zone-id agreement of zonal.stats -- in gloo process groups on a box without a GPU.  The
 product never imports this module (it has no CPU path); the kernels themselves are covered by the `-m gpu` tests."""
 import ctypes
@@ -11,6 +11,8 @@ import ctypes
 import numpy as np
 
 from oracle import xrs_oracle as orc
+from tests import classify_oracle as corc
+from xrspatial_amd import classify as cl
 
 _live = {}      # address -> ctypes buffer (keeps "device" allocations alive)
 
@@ -311,8 +313,22 @@ def call(name, *a):
         pad[kr // 2:kr // 2 + rows, kc // 2:kc // 2 + cols] = plane
         win = np.lib.stride_tricks.sliding_window_view(pad, (kr, kc))[y0:y0 + nb]
         _arr(dst, nb * cols * kr * kc, np.float32)[...] = np.where(k == 1, win, np.float32(np.nan)).ravel()
+    elif name.startswith("xrs_classify_bin_"):
+        i, o, n, bins, nv, nb, mode, _ = a
+        b = _arr(bins, nb, np.float64).copy()
+        assert int(mode) == cl.bin_mode(b), (int(mode), b)
+        _arr(o, n, np.float32)[...] = corc.bin_values(_arr(i, n, _CLASSIFY_DT[name.rsplit("_", 1)[1]]), b,
+                                                      _arr(nv, nb, np.float64))
+    elif name.startswith("xrs_classify_binary_"):
+        i, o, n, vals, nv, _ = a
+        dt = _CLASSIFY_DT[name.rsplit("_", 1)[1]]
+        _arr(o, n, dt)[...] = corc.binary(_arr(i, n, dt), _arr(vals, nv, np.float64).copy())
     else:
         raise NotImplementedError(f"fake_hip: {name} is not emulated")
+
+
+_CLASSIFY_DT = {"f32": np.float32, "f64": np.float64, "i8": np.int8, "u8": np.uint8, "i16": np.int16, "u16": np.uint16,
+                "i32": np.int32, "u32": np.uint32, "i64": np.int64, "u64": np.uint64}
 
 
 class _FakeLib:

@@ -1,7 +1,8 @@
 """Worker for test_gpu_parity.py::test_sharded_api_*: one rank of a row-sharded run through the PUBLIC API.
 
 Every rank builds a ShardedArray from its rows of a seeded raster and calls the same functions a single-GPU user
-calls (slope, hillshade, focal.mean, focal.apply, convolution_2d, ndvi, fuse(), zonal.stats); the neighbours' rows
+calls (slope, hillshade, focal.mean, focal.apply, convolution_2d, ndvi, fuse(), zonal.stats, classify.binary /
+reclassify); the neighbours' rows
 travel through the shard's transport -- tests/host_transport.HostTransport over gloo by default (which also works when all ranks
 share ONE GPU, as on the test box), distributed.Comm (RCCL) with XRS_TEST_TRANSPORT=rccl on a multi-GPU node.
 test_distributed_cpu.py runs the same worker without a GPU (XRS_TEST_FAKE_HIP=1)."""
@@ -12,6 +13,19 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+
+def classify_args(full):
+    """(output name, raster, function, kwargs) of the worker's classify calls; the tests that check them share it.  The
+    bins and values are cells of the DEM, so cells sit on edges and match values; the zones go through literal bins."""
+    fin = np.sort(full[np.isfinite(full)])
+    edges = [float(fin[int(q * (fin.size - 1))]) for q in (0.05, 0.35, 0.6, 0.95)]
+    many = [float(v) for v in fin[::fin.size // 90]]                        # > 64 sorted bins: the bisection
+    return [("binary_dem", "dem", "binary", {"values": [float(full[7, 11]), float(full[149, 0]), float(full[75, 150]), np.nan]}),
+            ("reclassify_dem", "dem", "reclassify", {"bins": edges + [np.inf], "new_values": [1.5, 2, 3, 4, 5]}),
+            ("reclassify_dem_search", "dem", "reclassify", {"bins": many, "new_values": list(range(len(many)))}),
+            ("binary_zones", "zones", "binary", {"values": [1, 4, 7]}),
+            ("reclassify_zones", "zones", "reclassify", {"bins": [5, 2, 8, 3], "new_values": [10, 20, 30, 40]})]
 
 
 def main(outdir):
@@ -86,11 +100,18 @@ def main(outdir):
     out['crosstab'] = ct.to_numpy(dtype=np.float64)
     out['crosstab_pct'] = zonal.crosstab(shard(zones_full), shard(cats_full), zone_ids=[1, 4, 7], cat_ids=[10, 14],
                                          agg='percentage').to_numpy(dtype=np.float64)
+    # classify: binary / reclassify go cell by cell on every rank's rows; a result is a shard of the input's geometry
+    from xrspatial_amd import classify
+    for name, key, fn, kw in classify_args(full):
+        res = getattr(classify, fn)(dem if key == "dem" else shard(zones_full), **kw)
+        assert isinstance(res.data, ShardedArray) and res.data.shape == (y1 - y0, W)
+        out[name] = res.data.get()
     # what a sharded raster cannot do fails loudly
     for bad in (lambda: zonal.stats(shard(zones_full), dem), lambda: focal.apply(shard(full, halo_cap=2), k7),
                 lambda: focal.apply(shard(full, halo_cap=2), k7, func=second_largest),
                 lambda: zonal.stats(shard(zones_full), dem, stats_funcs={'n': len}),
-                lambda: zonal.crosstab(shard(zones_full), dem),
+                lambda: zonal.crosstab(shard(zones_full), dem), lambda: classify.quantile(dem),
+                lambda: classify.maximum_breaks(dem),
                 lambda: xs.slope(xs.DataArray(dem.data, dims=['lat', 'lon'], coords={'lat': np.linspace(1, 2, y1 - y0),
                                                                                    'lon': np.linspace(1, 2, W)}), method='geodesic')):
         try:

@@ -175,3 +175,118 @@ def test_no_cpu_fallback():
                  lambda: xs.classify.reclassify(agg, [5, 10], [1, 2]), lambda: xs.classify.maximum_breaks(agg)):
         with pytest.raises(xs.XrsError):
             call()
+
+
+@pytest.mark.parametrize("fn", STAT_FUNCS)
+def test_numpy_reference_bins_reproduce_reference_bins(fn):
+    """tests/classify_oracle.py's bins (NumPy statistics, nothing of xrspatial_amd.classify) are the bins the
+    reference's own code handed to its bin pass, on every case of the fixture; where the reference raised, they raise
+    the same exception type."""
+    for case, a, kws in CASES:
+        key = f"{case}/{fn}"
+        with _quiet():
+            if key + "/exc" in FIX:
+                with pytest.raises(Exception) as ei:
+                    orc.bins_of(fn, a, **kws[fn])
+                assert type(ei.value).__name__ == str(FIX[key + "/exc"]), key
+                continue
+            bins = orc.bins_of(fn, a, **kws[fn])
+        if fn == "maximum_breaks" and FIX[key + "/bins"].size == 0:
+            assert len(bins) == 0, key
+            continue
+        _same_bins(bins, key)
+
+
+# ------------------------------------------------------------------ 64-bit integer extremes (float64 images -> dtype)
+def _images(vals):
+    """value_at for percentile_from_order_stats: the float64 image of the sorted cells, as the device returns it."""
+    s = np.sort(vals)
+    return lambda ranks: {int(r): float(s[int(r)]) for r in np.asarray(ranks).ravel()}
+
+
+def _extreme_rasters():
+    i64, u64 = np.iinfo(np.int64), np.iinfo(np.uint64)
+    mid = np.arange(-500, 500, 7)
+    # the widest gaps differ by far more than their float64 rounding, so the NumPy reference's picks are the device's
+    yield np.concatenate([mid, np.array([i64.max, i64.max - 1, 2 ** 62, i64.min, i64.min + 1, -2 ** 61], np.int64)])
+    yield np.concatenate([(mid + 1000).astype(np.uint64), np.array([u64.max, u64.max - 1, 2 ** 63, 2 ** 64 - 2 ** 12], np.uint64)])
+    yield np.array([0, i64.max, 7, 2 ** 62], np.int64)                          # the issue's four cells
+
+
+def test_from_f64_saturates_64_bit_integers():
+    i64, u64 = np.iinfo(np.int64), np.iinfo(np.uint64)
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")
+        np.testing.assert_array_equal(cl.from_f64([2.0 ** 63, -2.0 ** 63, 2.0 ** 62, -1.0, 0.0], np.int64),
+                                      [i64.max, i64.min, 2 ** 62, -1, 0])
+        np.testing.assert_array_equal(cl.from_f64([2.0 ** 64, 2.0 ** 63, 0.0], np.uint64), [u64.max, 2 ** 63, 0])
+        assert cl.from_f64(2.0 ** 63, np.int64)[()] == i64.max
+        for dt in (np.int8, np.uint16, np.int32, np.uint32, np.float32):              # exact images: a plain cast
+            np.testing.assert_array_equal(cl.from_f64([1.0, 2.0], dt), np.array([1, 2], dt))
+            assert cl.from_f64([1.0], dt).dtype == dt
+
+
+@pytest.mark.parametrize("which", [0, 1, 2])
+def test_percentiles_of_64_bit_extremes_do_not_wrap(which):
+    """The device's order statistics of a 64-bit raster are float64 images (2^63 for iinfo(int64).max): the restatement
+    must not flip their sign, stays within float64 rounding of np.percentile, and returns the exact min and max."""
+    a = list(_extreme_rasters())[which]
+    tol = 4 * np.spacing(np.max(np.abs(a.astype(np.float64))))
+    pct = [0, 1, 25, 33.3, 50, 90, 99.5, 99.9, 100]
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")
+        got = cl.percentile_from_order_stats(a.size, pct, a.dtype, _images(a))
+    want = np.percentile(a, pct)
+    assert got.dtype == want.dtype
+    assert np.all(np.sign(got) == np.sign(want)), (got, want)
+    assert np.all(np.abs(got - want) <= tol), (got - want)
+    assert got[0] == want[0] and got[-1] == want[-1]
+
+
+@pytest.mark.parametrize("which", [0, 1, 2])
+@pytest.mark.parametrize("k", [2, 3, 5, 70])
+def test_maximum_breaks_of_64_bit_extremes_do_not_wrap(which, k):
+    """maximum_breaks' host side fed the float64 images of a 64-bit raster (the picks path for k <= 65, every unique
+    value above): no OverflowError, no wrapped bin, every bin within float64 rounding of the NumPy reference's."""
+    a = list(_extreme_rasters())[which]
+    img = np.unique(a.astype(np.float64))                     # the device's unique values: images, merged where they round
+    tol = 4 * np.spacing(np.max(np.abs(img)))
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")
+        if k <= cl._MAX_BREAKS_MAX_TOP + 1:
+            gaps = np.diff(img)
+            order = sorted(range(len(gaps)), key=lambda i: (gaps[i], i))[-(k - 1):]
+            picks = [(i, img[i], img[i + 1]) for i in order]
+            bins, _ = cl.maximum_break_bins_from_picks(img.size, picks, img[-1], img[:k], k, a.dtype)
+        else:
+            bins, _ = cl.maximum_break_bins_from_unique(cl.from_f64(img, a.dtype), k)
+    want = orc.maximum_breaks_bins(a, k)
+    if img.size < k:                                          # every unique value: the images that round together merge
+        want = np.unique(cl.from_f64(want.astype(np.float64), a.dtype))
+    assert len(bins) == len(want), (bins, want)
+    bins, want = np.asarray(bins, np.float64), np.asarray(want, np.float64)
+    assert np.all(np.sign(bins) == np.sign(want)), (bins, want)
+    assert np.all(np.abs(bins - want) <= tol), (bins - want)
+    assert bins[-1] == float(a.max())
+
+
+def test_statistics_refuse_oversized_rasters_before_allocating(monkeypatch):
+    """The cell limits of the select (2^32 - 1) and of maximum_breaks' sort (2^31 - 1) are checked before any
+    workspace is sized or allocated: 2^32 float32 cells would ask for ~52 GiB and wrap `(int)n` in the C plan."""
+    def refuse(*a, **k):
+        raise AssertionError("allocated before the limit check")
+
+    monkeypatch.setattr(cl, "DeviceArray", refuse)
+    monkeypatch.setattr(cl._lib, "load", refuse)
+    monkeypatch.setattr(cl._lib, "call", refuse)
+    st = object.__new__(cl._Stats)
+    st.n, st.suffix = 1 << 32, "f32"
+    with pytest.raises(xs.XrsError, match=r"2\^31-1 cells"):
+        st.max_breaks(4)
+    with pytest.raises(xs.XrsError, match=r"2\^31-1 cells"):
+        st.max_breaks(-1)
+    with pytest.raises(xs.XrsError, match=r"2\^32-1 cells"):
+        st.select([0, 5])
+    st.n = (1 << 31)
+    with pytest.raises(xs.XrsError, match=r"2\^31-1 cells"):
+        st.max_breaks(2)

@@ -97,6 +97,13 @@ def test_sharded_api_host_logic(tmp_path, world):
         for p in parts:
             got[..., int(p["y0"]):int(p["y1"]), :] = p[name]
         np.testing.assert_array_equal(got, ref, err_msg=name)
+    # classify.binary / reclassify on the DEM and zone shards == tests/classify_oracle.py on the whole rasters
+    from tests import classify_oracle as corc
+    from tests.sharded_worker import classify_args
+    for name, key, fn, kw in classify_args(full):
+        src = full if key == "dem" else zones
+        ref = corc.binary(src, kw["values"]) if fn == "binary" else corc.bin_values(src, kw["bins"], kw["new_values"])
+        np.testing.assert_array_equal(np.concatenate([p[name] for p in parts]), ref, err_msg=name)
     # hotspots: block-wise convolution against GLOBAL moments combined from the ranks' (count, mean, ssd) triples
     want_hot, zscore = orc.hotspots(full, k7)
     got_hot = np.concatenate([p['hot7'] for p in parts])

@@ -3,7 +3,8 @@
 * 65536 x 65536 float32 DEM (16 GiB; 4.29e9 cells): slope, hillshade, the 5x5 circular focal mean and the fused pass,
   compared with the CPU oracle on row bands around every would-be 8-way shard boundary (rows 8192*k +- 16) -- which
   include the rows where the byte offset crosses 2^31 / 2^32 / 2^33 and the element offset crosses 2^31 -- plus the first
-  and the last 64 rows (element offsets up to 2^32 - 1, the raster's bottom edge).
+  and the last 64 rows (element offsets up to 2^32 - 1, the raster's bottom edge).  On the same DEM: classify's per-cell
+  passes on those bands, and the cell limits of its order statistics.
 * 32768 x 32768 float32 raster with 1000 int32 zones, blocky and scattered: zonal.stats against an exact host
   reduction (counts bit-exact; min / max exact; sums, means, variances against float64 host sums).
 
@@ -218,3 +219,55 @@ def test_s32_zonal_stats_1000_zones(vals32k, kind):
         np.testing.assert_allclose(df[col].to_numpy(), want, rtol=1e-9 if col in ('sum', 'mean') else 1e-6, err_msg=col)
     parity_log.record(cfg, 'min', df['min'].to_numpy(), mn, tol="bit-exact")
     parity_log.record(cfg, 'max', df['max'].to_numpy(), mx, tol="bit-exact")
+
+
+# ------------------------------------------------------------------ classify at 65536^2 = 2^32 cells
+def test_classify_per_cell_passes_at_2_32_cells(dem64k):
+    """reclassify (count and bisection), binary and equal_interval over 2^32 cells against tests/classify_oracle.py on
+    the bands of _bands64(), which cross the 2^31 and 2^32 element offsets; the finite count / min / max equal what
+    the host derives from BigRaster."""
+    from tests import classify_oracle as clo
+    from xrspatial_amd import classify as cl
+    blocks = dem64k.rows // PERIOD
+    agg = xs.DataArray(dem64k.dev, dims=['y', 'x'])
+    bands = {b: dem64k.host_rows(*b) for b in _bands64()}
+    n_fin = int(np.isfinite(dem64k.base).sum()) * blocks
+    lo = float(np.nanmin(dem64k.base))                                            # step > 0: the first copy holds the min
+    hi = float(np.nanmax(dem64k.base + dem64k.step * np.float32(blocks - 1)))    # float32 rounding is monotonic
+    cnt, mn, mx, _ = cl._Stats(dem64k.dev).moments()
+    assert (cnt, mn, mx) == (n_fin, lo, hi)
+    cells = np.concatenate([b[::7, ::4099].ravel() for b in bands.values()])
+    cells = cells[np.isfinite(cells)]
+    count_bins = list(np.sort(cells[:5]).astype(np.float64))
+    search_bins = list(np.unique(np.concatenate([np.linspace(lo, hi, 200), cells[:100].astype(np.float64)])))
+    values = [float(v) for v in cells[::max(1, cells.size // 12)]]
+    calls = [("reclassify", {"bins": count_bins, "new_values": np.arange(5) + 0.5},
+              lambda r: clo.bin_values(r, count_bins, np.arange(5) + 0.5), cl.BIN_COUNT),
+             ("reclassify", {"bins": search_bins, "new_values": np.arange(len(search_bins))},
+              lambda r: clo.bin_values(r, search_bins, np.arange(len(search_bins))), cl.BIN_SEARCH),
+             ("binary", {"values": values}, lambda r: clo.binary(r, values), None),
+             ("equal_interval", {"k": 7}, lambda r: clo.bin_values(r, clo.equal_interval_edges(lo, hi, 7), np.arange(7)), None)]
+    for fn, kw, ref, mode in calls:
+        if mode is not None:
+            assert cl.bin_mode(np.asarray(kw["bins"], np.float64)) == mode
+        out = getattr(xs.classify, fn)(agg, **kw).data
+        hits = 0
+        for (r0, r1), band in bands.items():
+            got, want = out.rows(r0, r1).get(), ref(band)
+            np.testing.assert_array_equal(got, want, err_msg=f"{fn} rows {r0}..{r1}")
+            hits += int(np.sum(got == 1)) if fn == "binary" else 0
+        assert fn != "binary" or hits >= len(values)
+        del out
+        parity_log.record("C4 65536^2 classify (bands at the 2^31 / 2^32 offsets)", fn, got, want, tol="bit-exact")
+
+
+def test_classify_statistics_refuse_2_32_cells(dem64k):
+    """The select takes at most 2^32 - 1 cells and maximum_breaks' sort 2^31 - 1: both refuse by name, and
+    maximum_breaks before it sizes its ~52 GiB sort workspace."""
+    agg = xs.DataArray(dem64k.dev, dims=['y', 'x'])
+    with pytest.raises(_lib.XrsError, match=r"2\^32-1 cells"):
+        xs.classify.quantile(agg, k=4)
+    with pytest.raises(_lib.XrsError, match=r"2\^31-1 cells"):
+        xs.classify.maximum_breaks(agg, k=5)
+    with pytest.raises(_lib.XrsError, match=r"2\^31-1 cells"):
+        xs.classify.maximum_breaks(agg, k=100)

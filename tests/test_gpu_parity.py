@@ -2602,6 +2602,13 @@ def test_sharded_api_equals_single_gpu(tmp_path, world):
         for col in table.columns:
             np.testing.assert_allclose(p['zonal_' + col].astype(np.float64), np.asarray(table[col], dtype=np.float64),
                                        rtol=1e-12, err_msg=col)
+    # sharded classify.binary / reclassify == the single-GPU results
+    from tests.sharded_worker import classify_args
+    from xrspatial_amd import classify
+    for name, key, fn, kw in classify_args(full):
+        src = full if key == "dem" else zones_full
+        ref = host(getattr(classify, fn)(xs.DataArray(xs.DeviceArray.from_numpy(src), dims=['y', 'x']), **kw).data)
+        np.testing.assert_array_equal(np.concatenate([p[name] for p in parts]), ref, err_msg=name)
     # sharded crosstab (per-rank counts + xrs_allreduce_u64) == the single-GPU table
     from xrspatial_amd import zonal
     H, W = zones_full.shape

@@ -26,6 +26,8 @@ BIN_LITERAL, BIN_COUNT, BIN_SEARCH = 0, 1, 2
 _COUNT_MAX_BINS = 64                    # wave-uniform count up to this many bins, bisection above
 _SELECT_MAX_RANKS = 64
 _MAX_BREAKS_MAX_TOP = 64
+_SELECT_MAX_CELLS = (1 << 32) - 1       # the limits of xrs_classify_select_* / xrs_classify_max_breaks_*, checked here
+_MAX_BREAKS_MAX_CELLS = (1 << 31) - 1   # before anything is allocated for them
 
 _BIN_SUFFIX = {np.dtype(np.float32): "f32", np.dtype(np.float64): "f64", np.dtype(np.int32): "i32",
                np.dtype(np.int64): "i64"}
@@ -57,6 +59,29 @@ def _resident(data):
 def _upload_f64(values):
     arr = np.ascontiguousarray(values, dtype=np.float64)
     return DeviceArray.from_numpy(arr if arr.size else np.zeros(1), stream=get_stream())
+
+
+def from_f64(values, dtype):
+    """float64 values (device order statistics, unique values) -> `dtype`.  A 64-bit integer dtype saturates to its
+    range: the device works on the float64 image of such a raster, where iinfo(int64).max reads as 2^63, and a plain
+    cast would wrap or raise.  Above 2^53 the image is already rounded, so saturating stays within that rounding."""
+    dtype = np.dtype(dtype)
+    x = np.asarray(values, dtype=np.float64)
+    if dtype.kind not in "iu" or dtype.itemsize < 8:
+        return x.astype(dtype)
+    top = x >= (2.0 ** 63 if dtype.kind == "i" else 2.0 ** 64)
+    out = np.where(top, 0.0, x).astype(dtype)
+    out[top] = np.iinfo(dtype).max
+    return out
+
+
+def _midpoints(lo, hi, dtype):
+    """(lo + hi) / 2.0 of the reference's maximum-breaks bins: in the raster's dtype (whose scalar overflow below 64 bits
+    the reference has and keeps), in float64 for a 64-bit integer dtype, where the sum of two large cells would wrap."""
+    dtype = np.dtype(dtype)
+    if dtype.kind in "iu" and dtype.itemsize == 8:
+        return np.array([(float(a) + float(b)) / 2.0 for a, b in zip(lo, hi)])
+    return np.array([(dtype.type(a) + dtype.type(b)) / 2.0 for a, b in zip(lo, hi)])
 
 
 def _as_f64(dev):
@@ -200,6 +225,8 @@ class _Stats:
 
     def select(self, ranks):
         """{rank: value} of the 0-based order statistics of the finite cells (exact, in the raster's dtype)."""
+        if self.n > _SELECT_MAX_CELLS:
+            raise _lib.XrsError(f"classify: order statistics take at most 2^32-1 cells per raster ({self.n})")
         ranks = np.unique(np.asarray(ranks, dtype=np.int64))
         vals = {}
         for i in range(0, ranks.size, _SELECT_MAX_RANKS):
@@ -213,6 +240,8 @@ class _Stats:
 
     def max_breaks(self, n_top):
         """(M, picks [(index, uv[index], uv[index + 1])], uv[M - 1], uv[:n_top + 1]); n_top < 0: (M, all of uv)."""
+        if self.n > _MAX_BREAKS_MAX_CELLS:         # before the sort workspace (~12 B/cell) is sized or allocated
+            raise _lib.XrsError(f"maximum_breaks: at most 2^31-1 cells per raster ({self.n})")
         if n_top < 0:
             out = DeviceArray((self.n + 1,), np.float64)
         else:
@@ -289,7 +318,7 @@ def percentile_from_order_stats(n, q_raw, dtype, value_at):
     vals = value_at(np.concatenate([rank(prev).ravel(), rank(nxt).ravel()]))
 
     def take(idx):
-        arr = np.asarray([vals[int(i)] for i in rank(idx).ravel()], dtype=np.float64).astype(dtype).reshape(idx.shape)
+        arr = from_f64([vals[int(i)] for i in rank(idx).ravel()], dtype).reshape(idx.shape)
         return arr[()]
 
     gamma = np.asanyarray(virtual - prev)
@@ -379,10 +408,10 @@ def maximum_break_bins_from_picks(m, picks, last, head, k, dtype):
     gaps (index, uv[index], uv[index + 1]), uv[-1] and the first unique values `head`."""
     dtype = np.dtype(dtype)
     if m < k:
-        return np.asarray(head[:m]).astype(dtype), np.arange(m)
+        return from_f64(head[:m], dtype), np.arange(m)
     idx = sorted(p for p in picks if p[0] >= 0)
-    bins = np.array([(dtype.type(a) + dtype.type(b)) / 2.0 for _, a, b in idx])
-    bins = np.append(bins, float(dtype.type(last)))
+    bins = _midpoints(from_f64([a for _, a, _ in idx], dtype), from_f64([b for _, _, b in idx], dtype), dtype)
+    bins = np.append(bins, float(from_f64(last, dtype)))
     return bins, np.arange(len(bins))
 
 
@@ -390,11 +419,12 @@ def maximum_break_bins_from_unique(uv, k):
     """The same for any k, from every unique value (k < 2: the reference keeps np.argsort(...)[-n:] with n <= 0)."""
     if len(uv) < k:
         return uv, np.arange(len(uv))
-    diffs = np.diff(uv)
+    wide = uv.dtype.kind in "iu" and uv.dtype.itemsize == 8
+    diffs = np.diff(uv.astype(np.float64) if wide else uv)        # a 64-bit gap in float64, as on the device: no wrap
     n_gaps = min(k - 1, len(diffs))
     top_indices = np.argsort(diffs, kind='stable')[-n_gaps:]
     top_indices.sort()
-    bins = np.array([(uv[i] + uv[i + 1]) / 2.0 for i in top_indices])
+    bins = _midpoints(uv[top_indices], uv[top_indices + 1], uv.dtype)
     bins = np.append(bins, float(uv[-1]))
     return bins, np.arange(len(bins))
 
@@ -495,7 +525,7 @@ def _run_maximum_breaks(data, k):
         bins, nv = maximum_break_bins_from_picks(m, picks, last, head, k, dtype)
     else:
         _, uv = st.max_breaks(-1)
-        bins, nv = maximum_break_bins_from_unique(uv.astype(dtype), k)
+        bins, nv = maximum_break_bins_from_unique(from_f64(uv, dtype), k)
     if len(bins) == 0:                 # no finite cell: the reference's loop never reads a bin, every cell is NaN
         bins, nv = np.zeros(1), np.zeros(1)
     return _classified(st, like_numpy, bins, nv)
