@@ -65,38 +65,86 @@ _OPTIMISTIC_WINDOW = 1 << 20         # bytes of the presence map filled during t
 _ZONE_DTYPE_CODE = {np.dtype(np.int32): 0, np.dtype(np.int64): 1, np.dtype(np.float32): 2, np.dtype(np.float64): 3}
 
 
-def _zone_table_device(zones_dev: DeviceArray):
-    """(unique ids, zmin, range, int32 DeviceArray table id - zmin -> dense index) for an integral zone raster in
-    HBM, without touching the raster on the host; None if the ids are not integral / too spread out / all invalid."""
-    code = _ZONE_DTYPE_CODE.get(zones_dev.dtype)
-    if code is None:
-        return None
-    stream = get_stream()
-    n = zones_dev.size
+def _scan(dev: DeviceArray, stream, window_map=None):
+    """(lo, hi, finite cells, all integral) of the ids in `dev`, as Python numbers: one xrs_zonal_scan -- or, with
+    `window_map` (int32 ids), xrs_zonal_scan_presence_i32, which also marks there the ids in [0, window_map.size)."""
     res = DeviceArray((4,), np.float64)
-    window_map = None
-    if code == 0:
-        # int32 ids: the scan marks ids in [0, 2^20) on the way, which usually makes the presence pass unnecessary
-        window_map = DeviceArray((_OPTIMISTIC_WINDOW,), np.uint8)
-        _lib.call("xrs_zonal_scan_presence_i32", zones_dev.ptr, n, res.ptr, window_map.ptr, _OPTIMISTIC_WINDOW, stream)
+    if window_map is None:
+        _lib.call("xrs_zonal_scan", dev.ptr, _ZONE_DTYPE_CODE[dev.dtype], dev.size, res.ptr, stream)
     else:
-        _lib.call("xrs_zonal_scan", zones_dev.ptr, code, n, res.ptr, stream)
+        _lib.call("xrs_zonal_scan_presence_i32", dev.ptr, dev.size, res.ptr, window_map.ptr, window_map.size, stream)
     raw = res.get(stream)
-    zmin, zmax = raw[0], raw[1]
-    n_finite = int(raw[2:3].view(np.uint64)[0])
-    all_integral = int(raw[3:4].view(np.int32)[0])
-    if n_finite == 0 or not all_integral or zmax - zmin >= _DENSE_RANGE_LIMIT:
-        return None
-    rng = int(zmax - zmin) + 1
-    if window_map is not None and zmin >= 0 and zmax < _OPTIMISTIC_WINDOW:
-        mask = window_map.get(stream)[int(zmin):int(zmax) + 1].astype(bool)
-    else:
-        present = DeviceArray((rng,), np.uint8)
-        _lib.call("xrs_zonal_presence", zones_dev.ptr, code, n, float(zmin), rng, present.ptr, stream)
-        mask = present.get(stream).astype(bool)
+    return float(raw[0]), float(raw[1]), int(raw[2:3].view(np.uint64)[0]), bool(raw[3:4].view(np.int32)[0])
+
+
+def _presence(dev: DeviceArray, lo, rng, stream):
+    """uint8 flags over [lo, lo + rng): which ids occur in `dev`."""
+    present = DeviceArray((rng,), np.uint8)
+    _lib.call("xrs_zonal_presence", dev.ptr, _ZONE_DTYPE_CODE[dev.dtype], dev.size, float(lo), rng, present.ptr, stream)
+    return present.get(stream)
+
+
+def _ids_from_presence(present, lo, dtype):
+    """The ids that presence flags over [lo, lo + len(present)) mark: (unique ids in `dtype`, int32 LUT id - lo -> dense
+    index with -1 for absent ids, lo, len(present)) -- the form every id discovery here returns."""
+    mask = np.asarray(present) > 0
     lut = np.where(mask, np.cumsum(mask, dtype=np.int64) - 1, -1).astype(np.int32)
-    uniq = (np.flatnonzero(mask).astype(np.float64) + zmin).astype(zones_dev.dtype)
-    return uniq, zmin, rng, DeviceArray.from_numpy(lut)
+    return (np.flatnonzero(mask).astype(np.float64) + lo).astype(dtype), lut, lo, len(mask)
+
+
+def _device_ids(zones_dev: DeviceArray, stream, max_range=_DENSE_RANGE_LIMIT, window=False):
+    """The ids of a zone raster in HBM, found without touching the raster on the host (_ids_from_presence; none when no
+    id is finite), or None when the ids are not integral or span `max_range` values or more -- rejected right after the
+    (min, max) scan, before the presence pass over the raster.  `window`: int32 ids in [0, _OPTIMISTIC_WINDOW) are marked
+    during the scan, which usually makes that pass unnecessary."""
+    if zones_dev.dtype not in _ZONE_DTYPE_CODE:
+        return None
+    window_map = DeviceArray((_OPTIMISTIC_WINDOW,), np.uint8) if window and zones_dev.dtype == np.int32 else None
+    lo, hi, n_finite, integral = _scan(zones_dev, stream, window_map)
+    if n_finite == 0:
+        return _ids_from_presence((), 0.0, zones_dev.dtype)
+    if not integral or hi - lo >= max_range:
+        return None
+    rng = int(hi - lo) + 1
+    if window_map is not None and lo >= 0 and hi < _OPTIMISTIC_WINDOW:
+        present = window_map.get(stream)[int(lo):int(hi) + 1]
+    else:
+        present = _presence(zones_dev, lo, rng, stream)
+    return _ids_from_presence(present, lo, zones_dev.dtype)
+
+
+def _zone_index(dev: DeviceArray, lo, rng, lut_dev: DeviceArray, stream):
+    """int32 DeviceArray of the dense index of every cell of `dev` through the LUT (-1: no zone); not synchronised."""
+    idx = DeviceArray(dev.shape, np.int32)
+    _lib.call("xrs_zonal_index", dev.ptr, _ZONE_DTYPE_CODE[dev.dtype], dev.size, float(lo), rng, lut_dev.ptr, idx.ptr, stream)
+    return idx
+
+
+def _indexed(dev: DeviceArray, ids, stream):
+    """(unique ids, int32 DeviceArray of dense indices) of `dev` from the `ids` that _device_ids / _sharded_ids found."""
+    uniq, lut, lo, rng = ids
+    if not rng:
+        return uniq, DeviceArray.from_numpy(np.full(dev.shape, -1, np.int32))
+    lut_dev = DeviceArray.from_numpy(lut)          # named: the kernel reads it until the sync below
+    idx = _zone_index(dev, lo, rng, lut_dev, stream)
+    _lib.call("xrs_stream_sync", stream)
+    return uniq, idx
+
+
+def _dense_index(data, upload=False):
+    """(unique finite ids, int32 DeviceArray of dense indices) of a host or device raster: mapped on the device when the ids
+    are integral and not too widely spread, on the host (_dense_zone_index) otherwise.  `upload`: NumPy ids are uploaded
+    for the device mapping first (zonal.stats: a host np.unique over the raster costs more than the whole reduction)."""
+    _lib.require_device()
+    dev = data if isinstance(data, DeviceArray) else None
+    if upload and dev is None and data.dtype in _ZONE_DTYPE_CODE and data.size:
+        dev = DeviceArray.from_numpy(np.ascontiguousarray(data))
+    ids = None if dev is None else _device_ids(dev, get_stream())
+    if ids is not None:
+        return _indexed(dev, ids, get_stream())
+    del dev                                        # (an uploaded copy is released before the host mapping)
+    uniq, idx = _dense_zone_index(data.get() if isinstance(data, DeviceArray) else np.asarray(data))
+    return uniq, DeviceArray.from_numpy(idx)
 
 
 _ONE_PASS_SAMPLES = 1 << 16          # cells of the strided sample that picks the id window and the shift
@@ -154,42 +202,6 @@ def _one_pass_partials(zones_dev: DeviceArray, vdev: DeviceArray, nodata_values)
     ids = (keep + base).astype(np.int32)
     return (ids, count[keep], host[off_s1:off_s2].view(np.float64)[keep], host[off_s2:off_mn].view(np.float64)[keep],
             host[off_mn:off_mx].view(vt)[keep], host[off_mx:off_pr].view(vt)[keep], shift)
-
-
-def _dense_zone_index_device(zones_dev: DeviceArray, max_range=None):
-    """Device-side counterpart of `_dense_zone_index` for zone rasters already in HBM: returns
-    (unique ids as a host array of the zones dtype, int32 DeviceArray of dense indices), or None when
-    the ids are not integral / span too wide a range (the caller then takes the host path).
-    `max_range`: give up right after the (min, max) scan -- before the presence and index passes over the raster -- when
-    the ids span more than that many values."""
-    code = _ZONE_DTYPE_CODE.get(zones_dev.dtype)
-    if code is None:
-        return None
-    stream = get_stream()
-    n = zones_dev.size
-    res = DeviceArray((4,), np.float64)
-    _lib.call("xrs_zonal_scan", zones_dev.ptr, code, n, res.ptr, stream)
-    raw = res.get(stream)
-    zmin, zmax = raw[0], raw[1]
-    n_finite = int(raw[2:3].view(np.uint64)[0])
-    all_integral = int(raw[3:4].view(np.int32)[0])
-    if n_finite == 0:
-        return zones_dev.get()[:0].ravel(), DeviceArray.from_numpy(np.full(zones_dev.shape, -1, np.int32))
-    if not all_integral or zmax - zmin >= _DENSE_RANGE_LIMIT:
-        return None
-    rng = int(zmax - zmin) + 1
-    if max_range is not None and rng > max_range:
-        return None
-    present = DeviceArray((rng,), np.uint8)
-    _lib.call("xrs_zonal_presence", zones_dev.ptr, code, n, float(zmin), rng, present.ptr, stream)
-    mask = present.get(stream).astype(bool)
-    lut = (np.cumsum(mask, dtype=np.int64) - 1).astype(np.int32)
-    uniq = (np.flatnonzero(mask).astype(np.float64) + zmin).astype(zones_dev.dtype)
-    lut_dev = DeviceArray.from_numpy(lut)
-    idx = DeviceArray(zones_dev.shape, np.int32)
-    _lib.call("xrs_zonal_index", zones_dev.ptr, code, n, float(zmin), rng, lut_dev.ptr, idx.ptr, stream)
-    _lib.call("xrs_stream_sync", stream)
-    return uniq, idx
 
 
 def _stage(zone_idx, values):
@@ -280,6 +292,14 @@ def zonal_partials(zone_idx, values, n_zones, nodata_values=None, comm=None, tab
 _MAJORITY_TABLE_LIMIT = 36864
 
 
+def _count_table(zidx: DeviceArray, cidx: DeviceArray, nz, nc, stream):
+    """(nz x nc) uint64 host table of the cells of every (zone index, category index) pair."""
+    cdev = DeviceArray((nz * nc,), np.uint64)
+    _lib.call("xrs_memset", cdev.ptr, 0, cdev.nbytes, stream)
+    _lib.call("xrs_crosstab_counts", zidx.ptr, cidx.ptr, zidx.size, nz, nc, cdev.ptr, stream)
+    return cdev.get(stream).reshape(nz, nc)
+
+
 def _majority_by_counting(zdev, vdev, n_zones, nodata_values, stream):
     """`majority` for CATEGORICAL values (integral, bounded range -- land-cover classes, integer DEMs): the values get
     dense category indices through the same scan / presence / index kernels as zone ids, (zone, category) pairs are
@@ -289,20 +309,17 @@ def _majority_by_counting(zdev, vdev, n_zones, nodata_values, stream):
     if n_zones == 0:
         return np.full(0, np.nan)
     # (rejected on the value RANGE right after the scan, before the presence and index passes over the raster)
-    cat = _dense_zone_index_device(vdev, max_range=_MAJORITY_TABLE_LIMIT // n_zones)
-    if cat is None:
+    ids = _device_ids(vdev, stream, max_range=_MAJORITY_TABLE_LIMIT // n_zones)
+    if ids is None:
         return None
-    cats, cidx = cat
+    cats, cidx = _indexed(vdev, ids, stream)
     nc = len(cats)
     out = np.full(n_zones, np.nan)
-    if nc == 0 or n_zones == 0:
+    if nc == 0:
         return out
     if n_zones * nc > _MAJORITY_TABLE_LIMIT:
         return None
-    cdev = DeviceArray((n_zones * nc,), np.uint64)
-    _lib.call("xrs_memset", cdev.ptr, 0, cdev.nbytes, stream)
-    _lib.call("xrs_crosstab_counts", zdev.ptr, cidx.ptr, zdev.size, n_zones, nc, cdev.ptr, stream)
-    counts = cdev.get(stream).reshape(n_zones, nc)
+    counts = _count_table(zdev, cidx, n_zones, nc, stream)
     if nodata_values is not None:
         counts[:, np.asarray(cats, dtype=np.float64) == float(nodata_values)] = 0
     best = counts.argmax(axis=1)
@@ -412,12 +429,45 @@ def finalize_stats(stat_names, count, s1, s2, mn, mx, majority=None, shift=0.0):
     return out
 
 
-def _stats_hip(zones_data, values_data, zone_ids, stat_names, nodata_values, return_type, comm=None, custom=None):
-    """`stat_names`: the output columns in order; `custom`: {name: callable} for the names that are not built in."""
+def _selection(unique_zones, zone_ids):
+    """Positions in `unique_zones` of the zones `zone_ids` selects -- the ids of np.unique(zone_ids) that occur, as the
+    reference takes them (zonal.py:290-296) -- or of every zone when it is None."""
+    if zone_ids is None:
+        return np.arange(len(unique_zones))
+    return np.flatnonzero(np.isin(unique_zones, np.unique(zone_ids)))
+
+
+def _stats_frame(unique_zones, keep, cols, stat_names, zone=None):
+    """The `stats` DataFrame of the selected zones `keep`: a 'zone' column of their ids (or `zone`), then the statistics."""
+    frame = {'zone': unique_zones[keep] if zone is None else zone}
+    for name in stat_names:
+        frame[name] = cols[name][keep]
+    return pd.DataFrame(frame)
+
+
+def _backproject(cols, stat_names, keep, nz, index, outs, stream):
+    """Back-projection (zonal.py:313-332): every cell of the dense index raster `index()` -- asked for once the table is
+    uploaded -- gets its zone's statistic, NaN outside the selected zones `keep`.  `outs`: one float64 buffer for all the
+    statistics, or one plane per statistic.  Not synchronised."""
+    width = max(nz, 1)
+    table = np.full((len(stat_names), width), np.nan)
+    for i, name in enumerate(stat_names):
+        table[i, keep] = cols[name][keep]
+    tdev = DeviceArray.from_numpy(table)
+    idx = index()
+    per = len(stat_names) // len(outs)
+    for k, out in enumerate(outs):
+        _lib.call("xrs_zonal_backproject_f64", idx.ptr, idx.size, tdev.ptr + k * per * width * 8, per, width, out.ptr, stream)
+
+
+def _stats_hip(zones_data, values_data, zone_ids, stat_names, nodata_values, return_type, custom=None):
+    """`stat_names`: the output columns in order; `custom`: {name: callable} for the names that are not built in.  The zone
+    ids are mapped by the first of: the one-pass window and the LUT table (int32-representable ids, partial-sum statistics
+    into a DataFrame), the dense index built on the device, the one built on the host."""
     like_numpy = not isinstance(values_data, DeviceArray)
     custom = custom or {}
     builtin = [n for n in stat_names if n not in custom]
-    mapped = None
+    stream = get_stream()
     small_int = zones_data.dtype in (np.int32, np.int16, np.int8, np.uint16, np.uint8)
     if (small_int and return_type == 'pandas.DataFrame' and 'majority' not in stat_names and not custom and int(zones_data.size) > 0
             and (isinstance(zones_data, np.ndarray) or zones_data.dtype == np.int32)):
@@ -428,104 +478,87 @@ def _stats_hip(zones_data, values_data, zone_ids, stat_names, nodata_values, ret
         if isinstance(zones_data, np.ndarray):
             zones_data = DeviceArray.from_numpy(np.ascontiguousarray(zones_data, dtype=np.int32))
         _, vdev = _stage(zones_data, values_data)
-        one = _one_pass_partials(zones_data, vdev, nodata_values) if comm is None else None
-        if one is not None:
-            # the ids were found by the reduction itself (no discovery pass: 8 B per cell in all)
-            unique_zones, count, s1, s2, mn, mx, shift = one
+        # the one-pass window finds the ids in the reduction itself (no discovery pass: 8 B per cell in all)
+        partials = _one_pass_partials(zones_data, vdev, nodata_values)
+        if partials is None:
+            ids = _device_ids(zones_data, stream, window=True)           # (int32 ids are all finite: never empty here)
+            if ids is not None:
+                unique_zones, lut, lo, rng = ids
+                # (the values staged for the one-pass attempt above: not uploaded a second time)
+                partials = (unique_zones,) + zonal_partials(zones_data, vdev, len(unique_zones), nodata_values,
+                                                            table=(lo, rng, DeviceArray.from_numpy(lut)))
+        if partials is not None:
+            unique_zones, count, s1, s2, mn, mx, shift = partials
             cols = finalize_stats(stat_names, count, s1, s2, mn, mx, None, shift)
-            keep = slice(None) if zone_ids is None else np.flatnonzero(np.isin(unique_zones, np.unique(zone_ids)))
-            frame = {'zone': unique_zones[keep]}
-            for name in stat_names:
-                frame[name] = cols[name][keep]
-            return pd.DataFrame(frame)
-        tab = _zone_table_device(zones_data)
-        if tab is not None:
-            unique_zones, zmin, rng, lut_dev = tab
-            nz = len(unique_zones)
-            # (the values staged for the one-pass attempt above: not uploaded a second time)
-            count, s1, s2, mn, mx, shift = zonal_partials(zones_data, vdev, nz, nodata_values, comm, table=(zmin, rng, lut_dev))
-            cols = finalize_stats(stat_names, count, s1, s2, mn, mx, None, shift)
-            if zone_ids is None:
-                keep = np.arange(nz)
-            else:
-                keep = np.flatnonzero(np.isin(unique_zones, np.unique(zone_ids)))
-            frame = {'zone': unique_zones[keep]}
-            for name in stat_names:
-                frame[name] = cols[name][keep]
-            return pd.DataFrame(frame)
-    if isinstance(zones_data, np.ndarray) and zones_data.dtype in _ZONE_DTYPE_CODE and zones_data.size:
-        # numpy zones: one upload, then the ids are mapped on the device (a host np.unique over the raster costs more
-        # than the whole reduction); non-integral / widely spread ids fall back to the host below
-        _lib.require_device()
-        zdev = DeviceArray.from_numpy(np.ascontiguousarray(zones_data))
-        mapped = _dense_zone_index_device(zdev)
-        del zdev
-    if isinstance(zones_data, DeviceArray):
-        _lib.require_device()
-        mapped = _dense_zone_index_device(zones_data)           # stays in HBM when ids are integral
-    if mapped is None:
-        zones_host = zones_data.get() if isinstance(zones_data, DeviceArray) else np.asarray(zones_data)
-        unique_zones, idx_host = _dense_zone_index(zones_host)
-        idx_dev = DeviceArray.from_numpy(idx_host)
-    else:
-        unique_zones, idx_dev = mapped
-    if zone_ids is None:
-        selected = unique_zones
-    else:
-        wanted = np.unique(zone_ids)
-        selected = [z for z in wanted if z in unique_zones]
+            return _stats_frame(unique_zones, _selection(unique_zones, zone_ids), cols, stat_names)
+    unique_zones, idx_dev = _dense_index(zones_data, upload=True)
     nz = len(unique_zones)
     _, vdev = _stage(idx_dev, values_data)
-    count, s1, s2, mn, mx, shift = zonal_partials(idx_dev, vdev, nz, nodata_values, comm)
-    # (the counts of THIS device's cells: with a communicator they have been added over the ranks and are not passed on)
-    majority = (zonal_majority(idx_dev, vdev, nz, nodata_values, counts=count if comm is None else None)
-                if 'majority' in builtin else None)
+    count, s1, s2, mn, mx, shift = zonal_partials(idx_dev, vdev, nz, nodata_values)
+    majority = zonal_majority(idx_dev, vdev, nz, nodata_values, counts=count) if 'majority' in builtin else None
     cols = finalize_stats(builtin, count, s1, s2, mn, mx, majority, shift)
-    keep = [i for i, z in enumerate(unique_zones) if z in selected]
+    keep = _selection(unique_zones, zone_ids)
     if custom:
         cols.update(_custom_columns(custom, idx_dev, vdev, nz, count, keep, nodata_values, np.dtype(values_data.dtype)))
     if return_type == 'pandas.DataFrame':
-        frame = {'zone': selected}
-        for name in stat_names:
-            frame[name] = cols[name][keep]
-        return pd.DataFrame(frame)
-    # back-projection (zonal.py:313-332): every cell gets its zone's statistic, NaN outside selected zones
-    table = np.full((len(stat_names), max(nz, 1)), np.nan)
-    for i, name in enumerate(stat_names):
-        table[i, keep] = cols[name][keep]
-    tdev = DeviceArray.from_numpy(table)
+        if zone_ids is None:
+            return _stats_frame(unique_zones, keep, cols, stat_names)
+        # the reference's zone column (zonal.py:290-296): the elements of np.unique(zone_ids) that occur, so in the dtype of
+        # zone_ids -- the table paths above give the zones' own ids
+        wanted = np.unique(zone_ids)
+        return _stats_frame(unique_zones, keep, cols, stat_names, zone=list(wanted[np.isin(wanted, unique_zones)]))
     out = DeviceArray((len(stat_names),) + tuple(idx_dev.shape), np.float64)
-    _lib.call("xrs_zonal_backproject_f64", idx_dev.ptr, idx_dev.size, tdev.ptr, len(stat_names), max(nz, 1), out.ptr,
-              get_stream())
-    return out.get(get_stream()) if like_numpy else out
+    _backproject(cols, stat_names, keep, nz, lambda: idx_dev, [out], stream)
+    return out.get(stream) if like_numpy else out
 
 
 _SHARDED_RANGE_LIMIT = 1 << 22      # widest span of zone ids whose presence map the ranks exchange
+
+
+def _sharded_ids(arr, stream, too_wide, not_integral=None):
+    """The ids of a row-sharded raster that every rank agrees on (_ids_from_presence; none when no rank holds a finite
+    id): the ranks all-reduce the id range -- with `not_integral`, also whether every id is integral, and raise
+    NotImplementedError(not_integral) when one is not -- and then the union of their presence maps.  A range wider than
+    _SHARDED_RANGE_LIMIT raises NotImplementedError(too_wide.format(rng=..., limit=...))."""
+    loc = arr.local
+    comm = arr.comm if arr.world > 1 else None
+    lo, hi, n_local, integral = _scan(loc, stream)
+    if not n_local:
+        lo, hi, integral = np.inf, -np.inf, True
+    if comm is not None:
+        mine = [lo, -hi] if not_integral is None else [lo, -hi, float(integral)]
+        agreed = [float(v) for v in comm.allreduce(np.array(mine), 'min')]           # one small all-reduce
+        lo, hi = agreed[0], -agreed[1]
+        integral = bool(agreed[-1]) if not_integral is not None else integral
+    if not_integral is not None and not integral:
+        raise NotImplementedError(not_integral)
+    if not np.isfinite(lo):
+        return _ids_from_presence((), 0.0, loc.dtype)
+    rng = int(hi - lo) + 1
+    if rng > _SHARDED_RANGE_LIMIT:
+        raise NotImplementedError(too_wide.format(rng=rng, limit=_SHARDED_RANGE_LIMIT))
+    seen = _presence(loc, lo, rng, stream)                    # uint8 flags: the union over the ranks is their maximum
+    if comm is not None:
+        seen = comm.allreduce(seen, 'max')
+    return _ids_from_presence(seen, lo, loc.dtype)
 
 
 def _stats_sharded(zones, values, zone_ids, stat_names, nodata_values, return_type):
     """zonal.stats of a row-sharded raster: every rank reduces its own rows to per-zone partial sums, the partials
     are all-reduced, and every rank finishes the same table -- the block partials + combine of the reference's dask
     path (zonal.py:181-277) with a collective in place of the task graph.  The set of zone ids is agreed on first
-    (global id range, then the union of the ranks' presence maps)."""
+    (_sharded_ids)."""
     same_layout(zones, values)
     if 'majority' in stat_names:
         raise NotImplementedError("'majority' needs a global sort and is not available for sharded rasters; "
                                   "pass stats_funcs without it")
     if zones.dtype != np.int32:
         raise TypeError("sharded zone rasters must be int32")
-    comm = zones.comm
     stream = get_stream()
     zloc = zones.local
-    res = DeviceArray((4,), np.float64)
-    _lib.call("xrs_zonal_scan", zloc.ptr, _ZONE_DTYPE_CODE[zloc.dtype], zloc.size, res.ptr, stream)
-    raw = res.get(stream)
-    n_local = int(raw[2:3].view(np.uint64)[0])
-    lo, hi = (raw[0], raw[1]) if n_local else (np.inf, -np.inf)
-    if comm is not None and zones.world > 1:
-        lo, neg_hi = (float(v) for v in comm.allreduce(np.array([lo, -hi]), 'min'))      # one small all-reduce
-        hi = -neg_hi
-    if not np.isfinite(lo):                                   # no rank holds a zone cell
+    unique_zones, lut, lo, rng = _sharded_ids(zones, stream,
+                                              "zone ids span {rng} values; sharded zonal.stats handles up to {limit}")
+    if not rng:                                               # no rank holds a zone cell
         if return_type == 'pandas.DataFrame':
             return pd.DataFrame({'zone': np.empty(0, np.int32), **{name: np.empty(0) for name in stat_names}})
         # back-projection of an empty table: every plane is NaN everywhere, sharded like the input
@@ -536,40 +569,19 @@ def _stats_sharded(zones, values, zone_ids, stat_names, nodata_values, return_ty
                 _lib.call("xrs_memcpy_h2d", plane.ptr, blank.ctypes.data, blank.nbytes, stream)
         _lib.call("xrs_stream_sync", stream)
         return ShardedStack(planes)
-    rng = int(hi - lo) + 1
-    if rng > _SHARDED_RANGE_LIMIT:
-        raise NotImplementedError(f"zone ids span {rng} values; sharded zonal.stats handles up to {_SHARDED_RANGE_LIMIT}")
-    present = DeviceArray((rng,), np.uint8)
-    _lib.call("xrs_zonal_presence", zloc.ptr, _ZONE_DTYPE_CODE[zloc.dtype], zloc.size, float(lo), rng, present.ptr, stream)
-    seen = present.get(stream)                                # uint8 flags: the union over the ranks is their maximum
-    if comm is not None and zones.world > 1:
-        seen = comm.allreduce(seen, 'max')
-    mask = np.asarray(seen) > 0
-    lut = np.where(mask, np.cumsum(mask, dtype=np.int64) - 1, -1).astype(np.int32)
-    unique_zones = (np.flatnonzero(mask).astype(np.float64) + lo).astype(np.int32)
     nz = len(unique_zones)
     vloc = values.local if values.dtype in (np.float32, np.float64) else values.local.astype(np.float64)
     lut_dev = DeviceArray.from_numpy(lut)                     # (named: read by the kernels below until their sync)
-    count, s1, s2, mn, mx, shift = zonal_partials(zloc, vloc, nz, nodata_values, comm if zones.world > 1 else None,
-                                           table=(lo, rng, lut_dev))
+    count, s1, s2, mn, mx, shift = zonal_partials(zloc, vloc, nz, nodata_values, zones.comm if zones.world > 1 else None,
+                                                  table=(lo, rng, lut_dev))
     cols = finalize_stats(stat_names, count, s1, s2, mn, mx, None, shift)
-    keep = np.arange(nz) if zone_ids is None else np.flatnonzero(np.isin(unique_zones, np.unique(zone_ids)))
+    keep = _selection(unique_zones, zone_ids)
     if return_type == 'pandas.DataFrame':
-        frame = {'zone': unique_zones[keep]}
-        for name in stat_names:
-            frame[name] = cols[name][keep]
-        return pd.DataFrame(frame)
-    # back-projection (zonal.py:313-332) of the agreed table onto this rank's rows: every plane is a shard again
-    table = np.full((len(stat_names), nz), np.nan)
-    for i, name in enumerate(stat_names):
-        table[i, keep] = cols[name][keep]
-    tdev = DeviceArray.from_numpy(table)
-    idx = DeviceArray(zloc.shape, np.int32)
-    _lib.call("xrs_zonal_index", zloc.ptr, _ZONE_DTYPE_CODE[zloc.dtype], zloc.size, float(lo), rng, lut_dev.ptr, idx.ptr, stream)
+        return _stats_frame(unique_zones, keep, cols, stat_names)
+    # the agreed table back-projected onto this rank's rows (the index raster only for this return): every plane is a shard
     planes = [values.like(np.float64) for _ in stat_names]
-    for i, plane in enumerate(planes):
-        _lib.call("xrs_zonal_backproject_f64", idx.ptr, idx.size, tdev.ptr + i * nz * 8, 1, nz, plane.ptr, stream)
-    _lib.call("xrs_stream_sync", stream)                      # idx / tdev / lut_dev are released on return
+    _backproject(cols, stat_names, keep, nz, lambda: _zone_index(zloc, lo, rng, lut_dev, stream), planes, stream)
+    _lib.call("xrs_stream_sync", stream)                      # the index / table / lut_dev are released on return
     return ShardedStack(planes)
 
 
@@ -662,6 +674,15 @@ def stats(
     return result
 
 
+def _dask_index(arr):
+    """(sorted unique finite values of dask-backed `arr`, the int32 dense index of each of its blocks, row by row; -1 for
+    non-finite cells): every block is computed here."""
+    nby, nbx = arr.numblocks
+    blocks = [np.asarray(arr.blocks[i, j].compute()) for i in range(nby) for j in range(nbx)]
+    uniq = np.unique(np.concatenate([np.unique(b[np.isfinite(b)]) for b in blocks]))
+    return uniq, [np.ascontiguousarray(np.where(np.isfinite(b), np.searchsorted(uniq, b), -1).astype(np.int32)) for b in blocks]
+
+
 def _stats_dask(zones, values, zone_ids, stat_names, nodata_values):
     """zonal.stats of dask-backed rasters: the reference's `_stats_dask_numpy` (zonal.py:181-277) -- per-block
     count / sum / sum of squares / min / max, combined by adding and reducing, mean / std / var from the combined sums
@@ -673,30 +694,19 @@ def _stats_dask(zones, values, zone_ids, stat_names, nodata_values):
     from .distributed import combine_zonal_partials
     if tuple(zones.chunks) != tuple(values.chunks):
         raise ValueError("zones and values must be chunked alike (zonal.py:198-199 pairs their blocks in order)")
-    nby, nbx = zones.numblocks
-    zblocks = [[np.asarray(zones.blocks[i, j].compute()) for j in range(nbx)] for i in range(nby)]
-    uniq = [np.unique(b[np.isfinite(b)]) if np.issubdtype(b.dtype, np.floating) else np.unique(b) for row in zblocks for b in row]
-    unique_zones = np.unique(np.concatenate(uniq)) if uniq else np.empty(0)
+    unique_zones, zidx = _dask_index(zones)
     nz = len(unique_zones)
     names = [n for n in stat_names if n != 'majority']
     if nz == 0:
         return pd.DataFrame({'zone': unique_zones, **{n: np.empty(0) for n in names}})
     parts = []
-    for i in range(nby):
-        for j in range(nbx):
-            zb = zblocks[i][j]
-            vb = np.ascontiguousarray(values.blocks[i, j].compute())
-            ok = np.isfinite(zb) if np.issubdtype(zb.dtype, np.floating) else np.ones(zb.shape, bool)
-            idx = np.where(ok, np.searchsorted(unique_zones, np.where(ok, zb, unique_zones[0])), -1).astype(np.int32)
-            _, vdev = _stage(idx, vb)
-            parts.append(zonal_partials(DeviceArray.from_numpy(np.ascontiguousarray(idx)), vdev, nz, nodata_values))
+    for k, idx in enumerate(zidx):
+        vb = np.ascontiguousarray(values.blocks[divmod(k, zones.numblocks[1])].compute())
+        _, vdev = _stage(idx, vb)
+        parts.append(zonal_partials(DeviceArray.from_numpy(idx), vdev, nz, nodata_values))
     count, s1, s2, mn, mx, shift = combine_zonal_partials(parts)
     cols = finalize_stats(names, count, s1, s2, mn, mx, None, shift)
-    keep = np.arange(nz) if zone_ids is None else np.flatnonzero(np.isin(unique_zones, np.unique(zone_ids)))
-    frame = {'zone': unique_zones[keep]}
-    for n in names:
-        frame[n] = cols[n][keep]
-    df = pd.DataFrame(frame)
+    df = _stats_frame(unique_zones, _selection(unique_zones, zone_ids), cols, names)
     try:                                                      # pragma: no cover (dask is not installable in the build image)
         import dask.dataframe as dd
         return dd.from_pandas(df, npartitions=1)
@@ -704,31 +714,13 @@ def _stats_dask(zones, values, zone_ids, stat_names, nodata_values):
         return df
 
 
-def _dense_index_any(data):
-    """(unique finite values, int32 DeviceArray of dense indices) for a host or device raster."""
-    if isinstance(data, DeviceArray):
-        _lib.require_device()
-        mapped = _dense_zone_index_device(data)
-        if mapped is not None:
-            return mapped
-        data = data.get()
-    uniq, idx = _dense_zone_index(np.asarray(data))
-    return uniq, DeviceArray.from_numpy(idx)
-
-
 def _crosstab_2d(zones_data, values_data, zone_ids, cat_ids, nodata_values, agg):
     # replaces _crosstab_numpy / _single_zone_crosstab_2d (zonal.py:699-800) for 2-D values
     _lib.require_device()
-    stream = get_stream()
-    unique_zones, zidx = _dense_index_any(zones_data)
-    all_cats, cidx = _dense_index_any(values_data)
+    unique_zones, zidx = _dense_index(zones_data)
+    all_cats, cidx = _dense_index(values_data)
     nz, nc = len(unique_zones), len(all_cats)
-    counts = np.zeros((nz, nc), dtype=np.uint64)
-    if nz and nc:
-        cdev = DeviceArray((nz * nc,), np.uint64)
-        _lib.call("xrs_memset", cdev.ptr, 0, cdev.nbytes, stream)
-        _lib.call("xrs_crosstab_counts", zidx.ptr, cidx.ptr, zidx.size, nz, nc, cdev.ptr, stream)
-        counts = cdev.get(stream).reshape(nz, nc)
+    counts = _count_table(zidx, cidx, nz, nc, get_stream()) if nz and nc else np.zeros((nz, nc), dtype=np.uint64)
     return _crosstab_frame(unique_zones, all_cats, counts, zone_ids, cat_ids, nodata_values, agg)
 
 
@@ -769,44 +761,13 @@ def _crosstab_frame(unique_zones, all_cats, counts, zone_ids, cat_ids, nodata_va
     return pd.DataFrame(frame)[['zone'] + list(sel_cats)]
 
 
-def _sharded_dense_index(arr, what):
-    """Dense indices of an integral row-sharded raster that every rank agrees on: (global unique values in the raster's
-    dtype, int32 DeviceArray of this rank's dense indices; -1 for non-finite cells).  The ranks all-reduce the value range
-    and then the union of their presence maps -- the protocol of `_stats_sharded`."""
-    comm, stream, loc = arr.comm, get_stream(), arr.local
-    code = _ZONE_DTYPE_CODE.get(loc.dtype)
-    if code is None:
+def _sharded_dense_index(arr, what, stream):
+    """Dense indices of an integral row-sharded raster that every rank agrees on (_sharded_ids): (global unique values in
+    the raster's dtype, int32 DeviceArray of this rank's dense indices; -1 for non-finite cells)."""
+    if arr.local.dtype not in _ZONE_DTYPE_CODE:
         raise TypeError(f"sharded {what} rasters must be int32 / int64 / float32 / float64")
-    res = DeviceArray((4,), np.float64)
-    _lib.call("xrs_zonal_scan", loc.ptr, code, loc.size, res.ptr, stream)
-    raw = res.get(stream)
-    n_local = int(raw[2:3].view(np.uint64)[0])
-    integral = float(int(raw[3:4].view(np.int32)[0]) if n_local else 1)
-    lo, hi = (raw[0], raw[1]) if n_local else (np.inf, -np.inf)
-    if comm is not None and arr.world > 1:
-        lo, neg_hi, integral = (float(v) for v in comm.allreduce(np.array([lo, -hi, integral]), 'min'))
-        hi = -neg_hi
-    if not integral:
-        raise NotImplementedError(f"sharded {what} rasters must hold integral values (categories)")
-    if not np.isfinite(lo):
-        return np.empty(0, loc.dtype), DeviceArray.from_numpy(np.full(loc.shape, -1, np.int32))
-    rng = int(hi - lo) + 1
-    if rng > _SHARDED_RANGE_LIMIT:
-        raise NotImplementedError(f"{what} values span {rng}; sharded rasters handle up to {_SHARDED_RANGE_LIMIT}")
-    present = DeviceArray((rng,), np.uint8)
-    _lib.call("xrs_zonal_presence", loc.ptr, code, loc.size, float(lo), rng, present.ptr, stream)
-    seen = present.get(stream)
-    if comm is not None and arr.world > 1:
-        seen = comm.allreduce(seen, 'max')
-    mask = np.asarray(seen) > 0
-    lut = np.where(mask, np.cumsum(mask, dtype=np.int64) - 1, -1).astype(np.int32)
-    uniq = (np.flatnonzero(mask).astype(np.float64) + lo).astype(loc.dtype)
-    idx = DeviceArray(loc.shape, np.int32)
-    lut_dev = DeviceArray.from_numpy(lut)          # named: the kernel reads it until the sync below (a temporary's block
-    _lib.call("xrs_zonal_index", loc.ptr, code, loc.size, float(lo), rng, lut_dev.ptr, idx.ptr, stream)   # would be recycled)
-    _lib.call("xrs_stream_sync", stream)
-    del lut_dev
-    return uniq, idx
+    return _indexed(arr.local, _sharded_ids(arr, stream, what + " values span {rng}; sharded rasters handle up to {limit}",
+                                            f"sharded {what} rasters must hold integral values (categories)"), stream)
 
 
 def _crosstab_2d_sharded(zones, values, zone_ids, cat_ids, nodata_values, agg):
@@ -816,18 +777,14 @@ def _crosstab_2d_sharded(zones, values, zone_ids, cat_ids, nodata_values, agg):
     same_layout(zones, values)
     _lib.require_device()
     stream = get_stream()
-    unique_zones, zidx = _sharded_dense_index(zones, "zone")
-    all_cats, cidx = _sharded_dense_index(values, "category")
+    unique_zones, zidx = _sharded_dense_index(zones, "zone", stream)
+    all_cats, cidx = _sharded_dense_index(values, "category", stream)
     nz, nc = len(unique_zones), len(all_cats)
     counts = np.zeros((nz, nc), dtype=np.uint64)
     if nz and nc:
-        cdev = DeviceArray((nz * nc,), np.uint64)
-        _lib.call("xrs_memset", cdev.ptr, 0, cdev.nbytes, stream)
-        _lib.call("xrs_crosstab_counts", zidx.ptr, cidx.ptr, zidx.size, nz, nc, cdev.ptr, stream)
-        counts = cdev.get(stream)
+        counts = _count_table(zidx, cidx, nz, nc, stream)
         if zones.comm is not None and zones.world > 1:
-            counts = zones.comm.allreduce(counts, 'sum')
-        counts = np.asarray(counts).reshape(nz, nc)
+            counts = np.asarray(zones.comm.allreduce(counts, 'sum')).reshape(nz, nc)
     return _crosstab_frame(unique_zones, all_cats, counts, zone_ids, cat_ids, nodata_values, agg)
 
 
@@ -841,28 +798,13 @@ def _crosstab_2d_dask(zones, values, zone_ids, cat_ids, nodata_values, agg):
     stream = get_stream()
     if tuple(zones.chunks) != tuple(values.chunks):
         raise ValueError("zones and values must be chunked alike (zonal.py:906-907 pairs their blocks in order)")
-    nby, nbx = zones.numblocks
-
-    def finite_unique(b):
-        return np.unique(b[np.isfinite(b)]) if np.issubdtype(b.dtype, np.floating) else np.unique(b)
-    zb = [[np.asarray(zones.blocks[i, j].compute()) for j in range(nbx)] for i in range(nby)]
-    vb = [[np.asarray(values.blocks[i, j].compute()) for j in range(nbx)] for i in range(nby)]
-    unique_zones = np.unique(np.concatenate([finite_unique(b) for row in zb for b in row]))
-    all_cats = np.unique(np.concatenate([finite_unique(b) for row in vb for b in row]))
+    unique_zones, zidx = _dask_index(zones)
+    all_cats, cidx = _dask_index(values)
     nz, nc = len(unique_zones), len(all_cats)
     counts = np.zeros((nz, nc), dtype=np.uint64)
-
-    def dense(b, uniq):
-        ok = np.isfinite(b) if np.issubdtype(b.dtype, np.floating) else np.ones(b.shape, bool)
-        return np.ascontiguousarray(np.where(ok, np.searchsorted(uniq, np.where(ok, b, uniq[0])), -1).astype(np.int32))
     if nz and nc:
-        for i in range(nby):
-            for j in range(nbx):
-                zidx, cidx = DeviceArray.from_numpy(dense(zb[i][j], unique_zones)), DeviceArray.from_numpy(dense(vb[i][j], all_cats))
-                cdev = DeviceArray((nz * nc,), np.uint64)
-                _lib.call("xrs_memset", cdev.ptr, 0, cdev.nbytes, stream)
-                _lib.call("xrs_crosstab_counts", zidx.ptr, cidx.ptr, zidx.size, nz, nc, cdev.ptr, stream)
-                counts += cdev.get(stream).reshape(nz, nc)
+        for zb, cb in zip(zidx, cidx):
+            counts += _count_table(DeviceArray.from_numpy(zb), DeviceArray.from_numpy(cb), nz, nc, stream)
     df = _crosstab_frame(unique_zones, all_cats, counts, zone_ids, cat_ids, nodata_values, agg)
     try:                                                      # pragma: no cover (dask is not installable in the build image)
         import dask.dataframe as dd
@@ -873,7 +815,7 @@ def _crosstab_2d_dask(zones, values, zone_ids, cat_ids, nodata_values, agg):
 
 def _crosstab_3d(zones_data, values_data, cat_labels, zone_ids, cat_ids, nodata_values, agg):
     # 3-D values: one layer per category, `agg` of the layer's values per zone (zonal.py:724-739)
-    unique_zones, zidx = _dense_index_any(zones_data)
+    unique_zones, zidx = _dense_index(zones_data)
     nz = len(unique_zones)
     sel_zones = unique_zones if zone_ids is None else [z for z in zone_ids if z in unique_zones]
     sel_cats = list(cat_labels) if cat_ids is None else [c for c in cat_ids if c in cat_labels]
