@@ -445,6 +445,19 @@ int xrs_zonal_backproject_f64(const int32_t *zone_idx_dev, int64_t n, const doub
 int xrs_match_bbox(const void *data_dev, int dtype, int64_t rows, int64_t cols, int64_t ld, const double *values,
                    int n_values, int invert, int *box4_dev, void *stream);
 
+/* zonal.regions (xrspatial/zonal.py:1406-1549 `_area_connectivity`, :1552-1636 `regions`): connected-region labels of a
+ * rows x cols C-contiguous raster (`dtype`: XRS_DT_*; at most 2^32 - 1 cells), 4- or 8-connected, with the reference's
+ * clamped windows and its tolerance abs_T(w - v) <= 1e-08 + 1e-05 * abs_T(v).  Two calls on one caller-owned
+ * workspace of xrs_regions_workspace_bytes(rows, cols) bytes, same raster and neighborhood:
+ *   xrs_regions_link:  links within tiles and counts the cells that open a new region; *n_new (host) receives the count,
+ *                      which is the largest label (the call waits for the stream);
+ *   xrs_regions_label: merges across tile borders and writes every cell's label into out_dev (same dtype; NaN kept). */
+size_t xrs_regions_workspace_bytes(int64_t rows, int64_t cols);
+int xrs_regions_link(const void *data_dev, int dtype, int64_t rows, int64_t cols, int neighborhood, void *work_dev,
+                     uint64_t *n_new, void *stream);
+int xrs_regions_label(const void *data_dev, int dtype, int64_t rows, int64_t cols, int neighborhood, void *work_dev,
+                      void *out_dev, void *stream);
+
 /* multispectral.true_color (xrspatial/multispectral.py:1334-1495).
  *   xrs_nan_minmax_f32: minmax_dev[0..1] = np.nanmin / np.nanmax of a float32 plane (NaN, NaN if it holds no number);
  *   xrs_true_color_u8:  rgba[i] = { stretch(red), stretch(green), stretch(blue), alpha } with

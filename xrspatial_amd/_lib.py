@@ -46,6 +46,9 @@ _PROTOTYPES = {
     "xrs_stream_mix_f32": [c_void_p, c_void_p, c_int, c_int64, c_void_p],
     "xrs_copy2d": [c_void_p, c_size_t, c_void_p, c_size_t, c_size_t, c_int64, c_void_p],
     "xrs_match_bbox": [c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_int, c_int, c_void_p, c_void_p],
+    "xrs_regions_workspace_bytes": [c_int64, c_int64],
+    "xrs_regions_link": [c_void_p, c_int, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p],
+    "xrs_regions_label": [c_void_p, c_int, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p],
     "xrs_nan_minmax_f32": [c_void_p, c_int64, c_void_p, c_void_p],
     "xrs_true_color_u8": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_double, c_double, c_double,
                           c_void_p, c_void_p],
@@ -174,7 +177,8 @@ _PROTOTYPES = {
 }
 _RESTYPES = {"xrs_kxk_workspace_bytes": c_size_t, "xrs_focal_workspace_bytes": c_size_t, "xrs_zonal_majority_workspace_bytes": c_size_t,
              "xrs_zonal_mode_workspace_bytes": c_size_t,
-             "xrs_geodesic_workspace_bytes": c_size_t, "xrs_classify_workspace_bytes": c_size_t}
+             "xrs_geodesic_workspace_bytes": c_size_t, "xrs_classify_workspace_bytes": c_size_t,
+             "xrs_regions_workspace_bytes": c_size_t}
 
 EXPORTED = tuple(_PROTOTYPES)
 

@@ -7,6 +7,7 @@ reference's own dask path, zonal.py:83-102), from which mean / std / var follow.
 """
 from __future__ import annotations
 
+import ctypes
 import os
 from typing import Dict, List, Optional, Union
 
@@ -949,3 +950,62 @@ def crop(zones, values, zones_ids, name='crop'):
     as `xrspatial.zonal.crop` (:1943-2061)."""
     top, bottom, left, right = _match_bounds(zones.data, zones_ids, invert=False)
     return _window(values, top, bottom, left, right, name)
+
+
+# ------------------------------------------------------------------ zonal.regions
+_REGIONS_MAX_CELLS = (1 << 32) - 1          # 32-bit cell indices in csrc/regions.hip, checked here before any allocation
+# the largest label each dtype holds exactly (the reference writes its ids into an array of the raster's dtype), and the
+# dtype to cast to when a raster has more regions than that
+_REGIONS_LIMIT = {np.dtype(t): (lim, wider) for t, lim, wider in (
+    (np.int8, 127, "int16"), (np.uint8, 255, "uint16"), (np.int16, 32767, "int32"), (np.uint16, 65535, "uint32"),
+    (np.int32, 2 ** 31 - 1, "int64"), (np.uint32, 2 ** 32 - 1, "uint64"), (np.int64, 2 ** 63 - 1, None),
+    (np.uint64, 2 ** 64 - 1, None), (np.float32, 2 ** 24, "float64"), (np.float64, 2 ** 53, None))}
+
+
+def regions(raster, neighborhood=4, name='regions'):
+    """Label each connected patch of equal-valued cells with its own id.  Same signature and result as
+    `xrspatial.zonal.regions` (zonal.py:1552-1636): 4- or 8-connectivity over the reference's clamped windows, its
+    relative tolerance (1e-05 * |v| + 1e-08, relative to the centre cell), ids numbered in the order in which each
+    region's first cell appears (with the reference's gaps), NaN cells kept, the input's dtype.
+
+    One deliberate difference: the reference writes its ids into an array of the raster's dtype and silently corrupts
+    them once a raster has more new ids than that dtype holds exactly (127 for int8, 255 for uint8, 2**24 for float32,
+    ...).  Here the ids are counted first and such a raster raises ValueError naming a wider dtype to cast to.
+    numpy-backed rasters are uploaded once and downloaded once; DeviceArray-backed ones stay in HBM."""
+    if neighborhood not in (4, 8):
+        raise ValueError("`neighborhood` value must be either 4 or 8)")
+    data = raster.data
+    if isinstance(data, ShardedArray):
+        raise NotImplementedError("zonal.regions of a row-sharded (multi-GPU) raster: merging regions across shards is "
+                                  "not implemented; gather the raster on one GPU")
+    if is_dask(data):
+        raise NotImplementedError("zonal.regions of a dask-backed raster: the reference has no dask path either; "
+                                  "compute the raster first")
+    if len(data.shape) != 2:
+        raise ValueError(f"zonal.regions: expected a 2D raster, got {len(data.shape)} dimensions")
+    dtype = np.dtype(data.dtype)
+    if dtype not in _REGIONS_LIMIT:
+        raise TypeError(f"zonal.regions: unsupported raster dtype {dtype}")
+    rows, cols = (int(s) for s in data.shape)
+    if rows * cols > _REGIONS_MAX_CELLS:
+        raise ValueError(f"zonal.regions: {rows} x {cols} cells exceed the 2**32 - 1 cells this backend labels")
+    _lib.require_device()
+    stream = get_stream()
+    if isinstance(data, DeviceArray):
+        dev, like_numpy = data, False
+    else:
+        dev, like_numpy = DeviceArray.from_numpy(np.ascontiguousarray(data), stream=stream), True
+    out = DeviceArray((rows, cols), dtype)
+    if rows * cols:
+        work = DeviceArray((_lib.load().xrs_regions_workspace_bytes(rows, cols),), np.uint8)
+        n_new = ctypes.c_uint64(0)
+        _lib.call("xrs_regions_link", dev.ptr, DTYPE_CODE[dtype], rows, cols, neighborhood, work.ptr, ctypes.byref(n_new),
+                  stream)
+        limit, wider = _REGIONS_LIMIT[dtype]
+        if n_new.value > limit:
+            raise ValueError(f"zonal.regions: the labels of this raster run up to {n_new.value}, more than {dtype} holds "
+                             f"exactly (at most {limit}); cast the raster to {wider} first")
+        _lib.call("xrs_regions_label", dev.ptr, DTYPE_CODE[dtype], rows, cols, neighborhood, work.ptr, out.ptr, stream)
+        _lib.call("xrs_stream_sync", stream)            # the workspace goes back to the pool
+    result = out.get(stream) if like_numpy else out
+    return DataArray(result, name=name, dims=raster.dims, coords=raster.coords, attrs=raster.attrs)
