@@ -191,10 +191,10 @@ def call(name, *a):
         z, code, n, zmin, rng, present, _ = a
         raw = _arr(z, n, (np.int32, np.int64, np.float32, np.float64)[code])
         raw = raw[np.isfinite(raw)] if code >= 2 else raw
-        ids = raw.astype(np.int64) - int(zmin)
+        off = np.trunc(raw.astype(np.float64) - float(zmin))        # the kernel's (long)((double)id - zmin)
         flags = _arr(present, rng, np.uint8)
         flags[...] = 0
-        flags[ids[(ids >= 0) & (ids < rng)]] = 1
+        flags[off[(off >= 0) & (off < rng)].astype(np.int64)] = 1
     elif name in ("xrs_zonal_init", "xrs_zonal_init_f64"):
         cnt, s1, s2, mn, mx, nz, _ = a
         vt = np.float64 if name.endswith("f64") else np.float32
@@ -268,9 +268,9 @@ def call(name, *a):
         z, code, n, zmin, rng, lut, idx, _ = a
         raw = _arr(z, n, (np.int32, np.int64, np.float32, np.float64)[code])
         fin = np.isfinite(raw) if code >= 2 else np.ones(n, bool)
-        off = np.where(fin, raw, 0).astype(np.int64) - int(zmin)
+        off = np.trunc(np.where(fin, raw, 0).astype(np.float64) - float(zmin))     # the kernel's (long)((double)id - zmin)
         inside = fin & (off >= 0) & (off < rng)
-        _arr(idx, n, np.int32)[...] = np.where(inside, _arr(lut, rng, np.int32)[np.clip(off, 0, rng - 1)], -1)
+        _arr(idx, n, np.int32)[...] = np.where(inside, _arr(lut, rng, np.int32)[np.clip(off, 0, rng - 1).astype(np.int64)], -1)
     elif name in ("xrs_zonal_partials_f64",):
         z, vals, n, nz, nodata, has_nodata, shift, cnt, s1, s2, mn, mx, _ = a
         idx = _arr(z, n, np.int32)

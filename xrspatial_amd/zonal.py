@@ -93,18 +93,31 @@ def _ids_from_presence(present, lo, dtype):
     return (np.flatnonzero(mask).astype(np.float64) + lo).astype(dtype), lut, lo, len(mask)
 
 
+_EXACT_DOUBLE = float(1 << 53)       # below this magnitude every integer is its own double
+
+
+def _beyond_double(dtype, lo, hi):
+    """Whether int64 ids with the scanned (lo, hi) cannot be mapped on the device.  The scan result and the `zmin` of the
+    presence / index entry points are doubles and the kernels take (double)id, so int64 ids of magnitude above 2^53
+    collapse onto their even neighbours.  The bound is >=: the scan has rounded already ((double)(2^53 + 1) == 2^53).
+    Float ids need no such rule: an integral float32 / float64 id is its own double, and the callers' range limits
+    (all far below 2^53) keep id - zmin exact."""
+    return dtype == np.int64 and (abs(lo) >= _EXACT_DOUBLE or abs(hi) >= _EXACT_DOUBLE)
+
+
 def _device_ids(zones_dev: DeviceArray, stream, max_range=_DENSE_RANGE_LIMIT, window=False):
     """The ids of a zone raster in HBM, found without touching the raster on the host (_ids_from_presence; none when no
-    id is finite), or None when the ids are not integral or span `max_range` values or more -- rejected right after the
-    (min, max) scan, before the presence pass over the raster.  `window`: int32 ids in [0, _OPTIMISTIC_WINDOW) are marked
-    during the scan, which usually makes that pass unnecessary."""
+    id is finite), or None when the ids are not integral, span `max_range` values or more, or are int64 ids that a
+    double does not hold (_beyond_double) -- rejected right after the (min, max) scan, before the presence pass over
+    the raster.  `window`: int32 ids in [0, _OPTIMISTIC_WINDOW) are marked during the scan, which usually makes that
+    pass unnecessary."""
     if zones_dev.dtype not in _ZONE_DTYPE_CODE:
         return None
     window_map = DeviceArray((_OPTIMISTIC_WINDOW,), np.uint8) if window and zones_dev.dtype == np.int32 else None
     lo, hi, n_finite, integral = _scan(zones_dev, stream, window_map)
     if n_finite == 0:
         return _ids_from_presence((), 0.0, zones_dev.dtype)
-    if not integral or hi - lo >= max_range:
+    if not integral or hi - lo >= max_range or _beyond_double(zones_dev.dtype, lo, hi):
         return None
     rng = int(hi - lo) + 1
     if window_map is not None and lo >= 0 and hi < _OPTIMISTIC_WINDOW:
@@ -134,7 +147,8 @@ def _indexed(dev: DeviceArray, ids, stream):
 
 def _dense_index(data, upload=False):
     """(unique finite ids, int32 DeviceArray of dense indices) of a host or device raster: mapped on the device when the ids
-    are integral and not too widely spread, on the host (_dense_zone_index) otherwise.  `upload`: NumPy ids are uploaded
+    are integral, not too widely spread and held by a double (_device_ids), on the host (_dense_zone_index, exact for every
+    integer dtype) otherwise.  `upload`: NumPy ids are uploaded
     for the device mapping first (zonal.stats: a host np.unique over the raster costs more than the whole reduction)."""
     _lib.require_device()
     dev = data if isinstance(data, DeviceArray) else None
@@ -535,6 +549,10 @@ def _sharded_ids(arr, stream, too_wide, not_integral=None):
         raise NotImplementedError(not_integral)
     if not np.isfinite(lo):
         return _ids_from_presence((), 0.0, loc.dtype)
+    if _beyond_double(loc.dtype, lo, hi):                     # (after the agreement: every rank refuses together)
+        raise NotImplementedError("sharded int64 rasters must hold ids of magnitude below 2^53: the ranks agree on the ids "
+                                  "through double-valued device passes, which merge larger ones, and a sharded raster "
+                                  "has no host mapping to fall back on")
     rng = int(hi - lo) + 1
     if rng > _SHARDED_RANGE_LIMIT:
         raise NotImplementedError(too_wide.format(rng=rng, limit=_SHARDED_RANGE_LIMIT))
@@ -892,14 +910,31 @@ def crosstab(zones, values, zone_ids=None, cat_ids=None, layer=None, agg="count"
 def _match_bounds(data, values, invert):
     """(top, bottom, left, right) of the cells that equal one of `values` (`invert`: that equal none), exactly as
     the reference's four scans leave them (zonal.py:1651-1731 `_trim`, :1845-1940 `_crop`) -- including the case
-    where no cell qualifies, in which every scan runs to the far edge.  One pass over the raster on the device."""
+    where no cell qualifies, in which every scan runs to the far edge.  One pass over the raster on the device, except
+    for a 64-bit integer raster and a wanted integer that a double does not hold (below)."""
     _lib.require_device()
-    vals = np.asarray(list(values), dtype=np.float64).reshape(-1)
+    values = list(values)
+    vals = np.asarray(values, dtype=np.float64).reshape(-1)
     if vals.size > 16:
         raise ValueError("at most 16 values are supported by the MI355X backend")
     if len(data.shape) != 2:
         raise ValueError("expected a 2D raster")
     rows, cols = data.shape
+    if data.dtype in (np.int64, np.uint64) and any(isinstance(v, (int, np.integer)) and abs(int(v)) >= _EXACT_DOUBLE for v in values):
+        # xrs_match_bbox compares (double)cell with double values: a wanted 2^53 + 1 would also match cells that hold
+        # 2^53.  The reference's `e == val` compares integers, so such a raster is compared on the host in its own dtype
+        # (one pass of NumPy `==` per value instead of one streaming pass on the device).  Cells beyond 2^53 compared
+        # with SMALLER wanted values are right on the device: rounding moves a cell by less than its distance to them.
+        host = data.get() if isinstance(data, DeviceArray) else np.asarray(data)
+        hit = np.zeros(host.shape, dtype=bool)
+        for v in values:
+            hit |= host == (int(v) if isinstance(v, (int, np.integer)) else v)
+        if invert:
+            hit = ~hit
+        ys, xs = np.flatnonzero(hit.any(axis=1)), np.flatnonzero(hit.any(axis=0))
+        if not ys.size:                       # nothing qualified
+            return max(rows - 1, 0), 0, max(cols - 1, 0), 0
+        return int(ys[0]), int(ys[-1]), int(xs[0]), int(xs[-1])
     if isinstance(data, DeviceArray):
         dev = data if data.dtype in DTYPE_CODE else data.astype(np.float32)
     else:
