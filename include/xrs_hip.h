@@ -458,6 +458,31 @@ int xrs_regions_link(const void *data_dev, int dtype, int64_t rows, int64_t cols
 int xrs_regions_label(const void *data_dev, int dtype, int64_t rows, int64_t cols, int neighborhood, void *work_dev,
                       void *out_dev, void *stream);
 
+/* perlin / generate_terrain (xrspatial/perlin.py:51-91 `_perlin`, `_perlin_numpy` and the 16 launches of `_perlin_cupy` /
+ * `_terrain_gpu`, :129-186 and terrain.py:130-180; terrain.py:36-80 `_gen_terrain`, `_terrain_numpy`): lattice noise with the
+ * NumPy path's typing.
+ *   xrs_noise_raw_*: ONE launch writes rows [row0, row0 + rows) of a total_rows x cols raster into out_dev (rows x cols,
+ *     C-contiguous) -- a banded or sharded plane is bit-identical to the whole one -- and leaves { min, max } of what it
+ *     wrote in minmax_dev[0..1] ({ +inf, -inf } for an empty call).  Coordinates are
+ *     np.linspace(x0, x1, cols, endpoint=False, dtype=float32) by np.linspace(y0, y1, total_rows, ...).  `tables`: HOST
+ *     array of n_octaves device pointers, table i = RandomState(seed + i).permutation(2^20) as int32 (not doubled).
+ *     mode 0 (perlin, n_octaves == 1): the noise stored in the output dtype (perlin.py:89).  mode 1 (terrain, up to 16
+ *     octaves): h = T(h + noise_i / 2^i) per octave, h / T(1.97), h ** 3 (terrain.py:50-60).  Every lattice index has to stay
+ *     in [0, 2^20 - 1); a range that does not is refused.
+ *   xrs_noise_finish_*: in place, (v - min) / (max - min) in the plane's dtype (perlin.py:90, terrain.py:76), then
+ *     v < threshold -> 0 (terrain.py:77) and v * scale (terrain.py:78) where asked for.  min / max pass through the host
+ *     between the two calls: a sharded caller reduces them across ranks there. */
+int xrs_noise_raw_f32(float *out_dev, int64_t rows, int64_t cols, int64_t row0, int64_t total_rows, double x0, double x1,
+                      double y0, double y1, const int32_t *const *tables, int n_octaves, int mode, double *minmax_dev,
+                      void *stream);
+int xrs_noise_raw_f64(double *out_dev, int64_t rows, int64_t cols, int64_t row0, int64_t total_rows, double x0, double x1,
+                      double y0, double y1, const int32_t *const *tables, int n_octaves, int mode, double *minmax_dev,
+                      void *stream);
+int xrs_noise_finish_f32(float *data_dev, int64_t n, double min, double max, int has_threshold, double threshold,
+                         int has_scale, double scale, void *stream);
+int xrs_noise_finish_f64(double *data_dev, int64_t n, double min, double max, int has_threshold, double threshold,
+                         int has_scale, double scale, void *stream);
+
 /* multispectral.true_color (xrspatial/multispectral.py:1334-1495).
  *   xrs_nan_minmax_f32: minmax_dev[0..1] = np.nanmin / np.nanmax of a float32 plane (NaN, NaN if it holds no number);
  *   xrs_true_color_u8:  rgba[i] = { stretch(red), stretch(green), stretch(blue), alpha } with

@@ -1,5 +1,5 @@
 """The reference's own asv benchmark suite (benchmarks/benchmarks/{slope,aspect,curvature,hillshade,focal,
-multispectral,zonal}.py) re-run on this backend with the same inputs and parametrisation:
+multispectral,zonal,perlin,terrain}.py) re-run on this backend with the same inputs and parametrisation:
 
   * rasters: `get_xr_dataarray` of benchmarks/benchmarks/common.py:8-61 -- ny = nx // 2, float64 Gaussian bump +
     N(0, 2) noise on lon/lat coordinates, seed 71942 (band rasters: seeds 100..700);
@@ -99,6 +99,10 @@ def main():
                 for ks in (5, 15):
                     kernel = np.ones((ks, ks))
                     record("focal.focal_stats", f"{ks}x{ks}", nx, kind, timeit(lambda: focal.focal_stats(agg, kernel)))
+            # perlin.py / terrain.py: default arguments on the suite's float64 raster (shape and backend are all they take
+            # from it); the permutation tables are cached on the device after the first call
+            for suite, fn in (("perlin", xs.perlin), ("generate_terrain", xs.generate_terrain)):
+                record(suite, "", nx, kind, timeit(lambda: fn(agg)))
             bands = {s: get_dataarray((ny, nx), kind, seed=s) for s in (100, 300, 400)}
             red, blue, nir = bands[100], bands[300], bands[400]
             for suite, fn in (("ndvi", lambda: xs.ndvi(nir, red)), ("evi", lambda: xs.evi(nir, red, blue)),

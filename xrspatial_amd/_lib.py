@@ -164,6 +164,12 @@ _PROTOTYPES = {
     "xrs_classify_above_f64": [c_void_p, c_int64, c_double, c_void_p, c_void_p, c_void_p],
     "xrs_classify_select_f64": [c_void_p, c_int64, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p],
     "xrs_classify_max_breaks_f64": [c_void_p, c_int64, c_int, c_void_p, c_size_t, c_void_p, c_void_p],
+    "xrs_noise_raw_f32": [c_void_p, c_int64, c_int64, c_int64, c_int64, c_double, c_double, c_double, c_double, c_void_p, c_int,
+                          c_int, c_void_p, c_void_p],
+    "xrs_noise_raw_f64": [c_void_p, c_int64, c_int64, c_int64, c_int64, c_double, c_double, c_double, c_double, c_void_p, c_int,
+                          c_int, c_void_p, c_void_p],
+    "xrs_noise_finish_f32": [c_void_p, c_int64, c_double, c_double, c_int, c_double, c_int, c_double, c_void_p],
+    "xrs_noise_finish_f64": [c_void_p, c_int64, c_double, c_double, c_int, c_double, c_int, c_double, c_void_p],
     "xrs_comm_unique_id": [c_void_p],
     "xrs_comm_init_rank": [ctypes.POINTER(c_void_p), c_void_p, c_int, c_int],
     "xrs_comm_destroy": [c_void_p],

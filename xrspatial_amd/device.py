@@ -88,9 +88,19 @@ def _raw_free(ptr: int, nbytes: int):
     _lib.load().xrs_free(ptr)
 
 
+_cache_clearers = []                     # other modules' device-side caches (perlin's permutation tables)
+
+
+def register_cache(clear):
+    """`clear()` is called by empty_cache() before the pooled blocks go back to the driver."""
+    _cache_clearers.append(clear)
+
+
 def empty_cache():
     """Return every cached device buffer to the driver and drop the recycled host blocks."""
     global _pool_bytes, _host_pool_bytes, _pinned_pool_bytes, _pinned_total_bytes
+    for clear in _cache_clearers:
+        clear()
     with _host_lock:
         _host_pool.clear()
         _host_pool_bytes = 0

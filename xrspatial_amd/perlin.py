@@ -1,0 +1,158 @@
+"""perlin: one octave of lattice noise, normalised to [0, 1].  Reference: xrspatial/perlin.py, its NumPy path.
+
+The noise and the plane's min / max come from one launch of csrc/noise.hip, the normalisation from a second, in-place one;
+between the two only the two scalars cross to the host (a row-sharded caller would reduce them across ranks there).
+What the host adds is the permutation table: `RandomState(seed).permutation(2**20)` -- the values of the reference's
+`np.random.seed(seed); np.random.permutation(2**20)` without touching NumPy's global state -- uploaded as int32 and kept in
+a small per-seed LRU on the device, because a permutation costs ~0.13 s of host time and generate_terrain needs 16.
+
+This module also holds what generate_terrain (terrain.py) shares with perlin: the table cache, the index validation and
+the two-launch runner.  There is no CPU fallback; dask- and ShardedArray-backed rasters raise NotImplementedError.
+"""
+from __future__ import annotations
+
+import ctypes
+import threading
+from collections import OrderedDict
+
+import numpy as np
+
+from . import _lib, device
+from ._launch import finish, get_stream
+from ._xr import DataArray
+from .device import DeviceArray
+from .utils import ArrayTypeFunctionMapping, not_implemented_func
+
+TABLE_SIZE = 1 << 20
+MODE_PERLIN, MODE_TERRAIN = 0, 1
+_SUFFIX = {np.dtype(np.float32): "f32", np.dtype(np.float64): "f64"}
+
+# ------------------------------------------------------------------ permutation tables, cached on the device per seed
+_TABLE_CACHE_MAX = 32                    # 4 MiB each: two terrains' worth of octaves
+_tables = OrderedDict()                  # seed -> DeviceArray (int32, 2^20)
+_tables_lock = threading.RLock()
+_counters = {"uploads": 0, "hits": 0}
+
+
+def host_table(seed):
+    """The reference's permutation for `seed` (perlin.py:80-81, terrain.py:51-52), int32, not doubled."""
+    return np.random.RandomState(seed).permutation(TABLE_SIZE).astype(np.int32)
+
+
+def device_tables(seeds):
+    """DeviceArrays of the tables of `seeds`, from the cache where they are there."""
+    out = []
+    with _tables_lock:
+        for seed in seeds:
+            tab = _tables.get(seed)
+            if tab is None:
+                tab = DeviceArray.from_numpy(host_table(seed), stream=get_stream())
+                _counters["uploads"] += 1
+                _tables[seed] = tab
+            else:
+                _counters["hits"] += 1
+                _tables.move_to_end(seed)
+            out.append(tab)
+        while len(_tables) > max(_TABLE_CACHE_MAX, len(out)):
+            _tables.popitem(last=False)
+    return out
+
+
+def table_cache_info():
+    """{'uploads': tables built and uploaded, 'hits': tables served from the cache, 'size': tables held}."""
+    with _tables_lock:
+        return dict(_counters, size=len(_tables))
+
+
+def clear_table_cache():
+    with _tables_lock:
+        _tables.clear()
+
+
+device.register_cache(clear_table_cache)           # xrspatial_amd.empty_cache() drops the tables too
+
+
+# ------------------------------------------------------------------ argument checks (before any device work)
+def check_dtype(data, what):
+    if len(data.shape) != 2:
+        raise ValueError(f"{what}: a 2-D raster is needed, got {len(data.shape)} dimensions")
+    if np.dtype(data.dtype) not in _SUFFIX:
+        raise ValueError(f"{what}: float32 or float64 data is needed, got {np.dtype(data.dtype)}")
+
+
+def linspace_ends(a, b, n):
+    """Smallest and largest element of np.linspace(a, b, n, endpoint=False, dtype=np.float32): its two ends."""
+    a, b = float(a), float(b)
+    first, last = np.float32(a), np.float32(float(n - 1) * ((b - a) / n) + a)
+    return min(first, last), max(first, last)
+
+
+def check_lattice(what, x_range, y_range, shape, n_octaves):
+    """Every lattice index trunc(coordinate * 2^octave) has to stay in [0, 2^20 - 1): the tables have 2^20 entries and
+    index + 1 is read.  (The reference wraps a negative index to the table's end and raises IndexError beyond it.)"""
+    rows, cols = shape
+    top = np.float32(2.0 ** (n_octaves - 1))
+    for axis, (a, b), n in (("x", x_range, cols), ("y", y_range, rows)):
+        if not (np.isfinite(a) and np.isfinite(b)):
+            raise ValueError(f"{what}: the {axis} range ({a}, {b}) is not finite")
+        if n == 0:
+            continue
+        lo, hi = linspace_ends(a, b, n)
+        if lo < 0 or not float(hi) * float(top) < TABLE_SIZE - 1:
+            raise ValueError(f"{what}: lattice coordinates [{float(lo) * float(top):g}, {float(hi) * float(top):g}] along {axis} leave "
+                             f"[0, 2**20 - 1)")
+
+
+# ------------------------------------------------------------------ the two launches
+def raw_plane(out, seeds, x_range, y_range, mode, row0=0, total_rows=None):
+    """Launch the noise kernel for rows [row0, row0 + out.shape[0]) of a `total_rows`-high raster into `out`; returns the
+    (min, max) of what it wrote."""
+    rows, cols = out.shape
+    tables = device_tables(seeds)
+    ptrs = (ctypes.c_void_p * len(tables))(*[t.ptr for t in tables])
+    slot = DeviceArray((2,), np.float64)
+    _lib.call("xrs_noise_raw_" + _SUFFIX[out.dtype], out.ptr, rows, cols, row0, rows if total_rows is None else total_rows,
+              float(x_range[0]), float(x_range[1]), float(y_range[0]), float(y_range[1]), ptrs, len(tables), mode, slot.ptr,
+              get_stream())
+    mn, mx = slot.get(get_stream())
+    return float(mn), float(mx)
+
+
+def finish_plane(out, mn, mx, threshold=None, scale=None):
+    """(v - mn) / (mx - mn) in place, then `v < threshold -> 0` and `v * scale` where given."""
+    _lib.call("xrs_noise_finish_" + _SUFFIX[out.dtype], out.ptr, out.size, mn, mx, int(threshold is not None),
+              float(0.0 if threshold is None else threshold), int(scale is not None), float(1.0 if scale is None else scale),
+              get_stream())
+
+
+def run(data, seeds, x_range, y_range, mode, threshold=None, scale=None):
+    """The whole pipeline for one raster: a NumPy raster gets NumPy back, a DeviceArray a DeviceArray."""
+    _lib.require_device()
+    out = DeviceArray(tuple(data.shape), data.dtype)
+    if out.size:
+        mn, mx = raw_plane(out, seeds, x_range, y_range, mode)
+        finish_plane(out, mn, mx, threshold, scale)
+    return finish(out, isinstance(data, np.ndarray))
+
+
+def _run_perlin(data, freq, seed):
+    return run(data, [seed], (0, freq[0]), (0, freq[1]), MODE_PERLIN)
+
+
+def perlin(agg, freq=(1, 1), seed=5, name='perlin'):
+    """Perlin noise over `agg`'s shape, normalised to [0, 1] (a constant plane, 1 x 1 for instance, is NaN as upstream).
+
+    agg: 2-D float32 / float64 DataArray; its backend (NumPy or DeviceArray) and dtype are the result's.  freq: (x, y)
+    frequency multipliers, non-negative and below 2**20.  seed: seed of the permutation table.  Same signature and
+    results as `xrspatial.perlin` (NumPy path; the result keeps agg's dims and attrs)."""
+    check_dtype(agg.data, "perlin")
+    if len(freq) != 2:
+        raise ValueError("perlin: freq must be (x, y)")
+    check_lattice("perlin", (0, freq[0]), (0, freq[1]), agg.shape, 1)
+    mapper = ArrayTypeFunctionMapping(
+        numpy_func=_run_perlin, hip_func=_run_perlin,
+        sharded_func=lambda *args: not_implemented_func(
+            *args, messages='perlin() does not support row-sharded (multi-GPU) DataArray'),
+        dask_func=lambda *args: not_implemented_func(*args, messages='perlin() does not support dask backed DataArray'))
+    out = mapper(agg)(agg.data, freq, int(seed))
+    return DataArray(out, dims=agg.dims, attrs=agg.attrs, name=name)
