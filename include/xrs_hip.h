@@ -483,6 +483,20 @@ int xrs_noise_finish_f32(float *data_dev, int64_t n, double min, double max, int
 int xrs_noise_finish_f64(double *data_dev, int64_t n, double min, double max, int has_threshold, double threshold,
                          int has_scale, double scale, void *stream);
 
+/* viewshed (xrspatial/viewshed.py, the CPU sweep `_viewshed_cpu` / `_viewshed_cpu_sweep`): which cells of a rows x cols
+ * C-contiguous raster (both at least 2) are seen from cell (view_row, view_col), as a per-cell predicate that equals the
+ * sweep's result.  All arithmetic is float64 whatever the raster's dtype; the viewpoint's elevation is
+ * data[view_row, view_col] + observer_elev, read on the device.  ew_res / ns_res: the coordinate steps along x / y (only
+ * their squares matter).  out_dev (float64): 180 at the viewpoint, -1 where invisible, else the vertical angle in degrees
+ * (`_get_vertical_ang`).  NaN cells are never visible and never hide a cell.  Two launches on the stream: the three event
+ * gradients of every cell into work_dev (xrs_viewshed_workspace_bytes(rows, cols) bytes, caller-owned), then one ray walk
+ * per cell. */
+size_t xrs_viewshed_workspace_bytes(int64_t rows, int64_t cols);
+int xrs_viewshed_f32(const float *data_dev, int64_t rows, int64_t cols, int64_t view_row, int64_t view_col, double observer_elev,
+                     double target_elev, double ew_res, double ns_res, void *work_dev, double *out_dev, void *stream);
+int xrs_viewshed_f64(const double *data_dev, int64_t rows, int64_t cols, int64_t view_row, int64_t view_col, double observer_elev,
+                     double target_elev, double ew_res, double ns_res, void *work_dev, double *out_dev, void *stream);
+
 /* multispectral.true_color (xrspatial/multispectral.py:1334-1495).
  *   xrs_nan_minmax_f32: minmax_dev[0..1] = np.nanmin / np.nanmax of a float32 plane (NaN, NaN if it holds no number);
  *   xrs_true_color_u8:  rgba[i] = { stretch(red), stretch(green), stretch(blue), alpha } with

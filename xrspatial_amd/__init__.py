@@ -4,7 +4,7 @@ Drop-in for the `xrspatial.*` functions on that path (same names, signatures, Da
 in/out): slope, aspect, hillshade, curvature, focal.mean / apply / focal_stats,
 convolution.convolve_2d / convolution_2d, multispectral ndvi / evi / savi (+ nbr, nbr2, ndmi),
 zonal.stats, zonal.regions, classify (binary, reclassify, equal_interval, quantile, percentiles, box_plot, std_mean,
-head_tail_breaks, maximum_breaks), perlin, generate_terrain.  Python host code calling hand-written HIP kernels through the C ABI of
+head_tail_breaks, maximum_breaks), perlin, generate_terrain, viewshed.  Python host code calling hand-written HIP kernels through the C ABI of
 libxrs_hip.so (include/xrs_hip.h); no PyTorch, CuPy, Numba or Triton involved.
 
     import xrspatial_amd as xrspatial        # numpy-backed DataArray in -> numpy-backed out
@@ -29,6 +29,7 @@ from .multispectral import arvi, evi, nbr, ndvi, savi, sipi  # noqa: F401
 from .perlin import perlin  # noqa: F401
 from .slope import slope  # noqa: F401
 from .terrain import generate_terrain  # noqa: F401
+from .viewshed import viewshed  # noqa: F401
 from .zonal import crosstab as zonal_crosstab  # noqa: F401
 from .zonal import regions  # noqa: F401
 from .zonal import stats as zonal_stats  # noqa: F401
