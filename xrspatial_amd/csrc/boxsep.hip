@@ -494,11 +494,7 @@ int launch_box_sep(const float *in, float *out_sum, float *out_mean, float *out_
         }
     }
     // tile height: whole rounds of resident workgroups, each tile paying 2 ry rows of run-in (as walk3_tile_base)
-    static thread_local int n_cu = 0;
-    if (!n_cu) {
-        hipDeviceProp_t prop;
-        n_cu = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-    }
+    const int n_cu = device_cu_count();
     int wg_cu = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&wg_cu, reinterpret_cast<const void *>(fn), 256, lds) != hipSuccess || wg_cu < 1) wg_cu = 1;
     const long slots = (long)n_cu * wg_cu;

@@ -9,7 +9,7 @@
 // No LDS, no barriers.  Reference semantics: xrspatial/focal.py:226-258 (numba reducers) over the cells under
 // `kernel == 1` in row-major order (:268-326), NaN cells skipped, window clipped at the raster edge.
 #pragma once
-#include "xrs_common.h"
+#include "window_call.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -20,28 +20,7 @@ namespace xrs {
 
 constexpr int CTH = 128;     // output rows per tile (input rows walked: CTH + 2R)
 
-// Mask shapes the walkers are instantiated for: every row of the (2R+1)^2 mask is ONE run centred on the kernel's
-// centre column, with a compile-time half-width hw(R, |dy|).
-struct CircleShape {      // circle_kernel on square cells: largest dx with dx^2 + dy^2 <= R^2 (convolution.py:144)
-    static constexpr int hw(int R, int dy) {
-        int h = 0;
-        while ((h + 1) * (h + 1) + dy * dy <= R * R) ++h;
-        return h;
-    }
-    static constexpr int hwi(int, int) { return -1; }      // no hole
-};
-struct BoxShape {         // np.ones((2R+1, 2R+1))
-    static constexpr int hw(int R, int) { return R; }
-    static constexpr int hwi(int, int) { return -1; }
-};
-// annulus_kernel(1, 1, R, RI) = circle_kernel(R) - circle_kernel(RI) (convolution.py:199-259): a row at offset dy is the
-// centred run of half-width hw(dy) WITHOUT the centred run of half-width hwi(dy) (-1: no hole in this row) -- two runs,
-// but every sum over them is a difference of two centred-run sums, and every extremum one over a "shell" of cell pairs.
-template <int RI>
-struct AnnulusShape {
-    static constexpr int hw(int R, int dy) { return CircleShape::hw(R, dy); }
-    static constexpr int hwi(int, int dy) { return dy <= RI ? CircleShape::hw(RI, dy) : -1; }
-};
+// (the mask shapes -- CircleShape, BoxShape, AnnulusShape<RI> -- and their row formulas: window_call.h)
 template <typename Shape>
 constexpr bool shape_has_hole(int R) {
     for (int dy = 0; dy <= R; ++dy)
@@ -83,28 +62,6 @@ constexpr int shape_taps(int R) {
     int n = 0;
     for (int dy = -R; dy <= R; ++dy) n += shape_row_cells<Shape>(R, dy < 0 ? -dy : dy);
     return n;
-}
-
-// host: the inner radius of a K x K mask that could be annulus_kernel(1, 1, K / 2, RI): the zeros of the centre row run from
-// the centre to dx = RI (circle_kernel(RI) has half-width RI in its middle row); -1: the centre cell is set (no hole)
-inline int annulus_inner_radius(const double *kernel, int K) {
-    const int R = K / 2;
-    int ri = -1;
-    while (ri + 1 <= R && kernel[R * K + R + ri + 1] != 1.0) ++ri;
-    return ri;
-}
-
-template <int R, typename Shape>
-inline bool is_shape(const double *kernel) {
-    constexpr int K = 2 * R + 1;
-    for (int ky = 0; ky < K; ++ky) {
-        const int dy = ky < R ? R - ky : ky - R, h = Shape::hw(R, dy), hi = Shape::hwi(R, dy);
-        for (int kx = 0; kx < K; ++kx) {
-            const int dx = kx < R ? R - kx : kx - R;
-            if ((kernel[ky * K + kx] == 1.0) != (dx <= h && dx > hi)) return false;
-        }
-    }
-    return true;
 }
 
 // a[s] <- a[(s + U) mod K] for every s, in place: the permutation is gcd(K, U) cycles of length K / gcd, walked with
@@ -172,13 +129,7 @@ inline int walk3_wg_per_cu(K kernel_fn, int fallback) {
 }
 
 inline int walk3_tile_base(long rows, long groups_x, int radius, int u, int wg_per_cu) {
-    static thread_local int n_cu = 0;
-    if (!n_cu) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        n_cu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-                   ? prop.multiProcessorCount : 256;
-    }
+    const int n_cu = device_cu_count();
     // (radius < 10, or a raster too short to fill the chip several times: 128 -- the lighter kernels of small windows are
     //  bound by HBM, not by rounds, and measured 10-15 % slower on 256-row tiles: box 11x11 seven statistics 2.39 vs 2.75 ms)
     if (radius < 10 || rows < 8192) return 128;
@@ -236,6 +187,11 @@ struct WalkGeom {
     int halo_top, halo_bot;
     long tiles_x, n_tiles;
 };
+// host: the call's plane and geometry (tiles_x / n_tiles are the launcher's)
+inline void fill_geom(WalkGeom &g, const WindowCall &c) {
+    g.in = c.in; g.rows = c.rows; g.cols = c.cols; g.ld_in = c.ld_in; g.ld_out = c.ld_out;
+    g.halo_top = c.halo_top; g.halo_bot = c.halo_bot;
+}
 
 // The 2R+1 cells of input row yy around column x (NaN outside the raster / the shard's halo rows).
 // EDGE = false: the wave's columns xw - R .. xw + 63 + R all lie inside the raster (wave-uniform fact): no column tests.
@@ -696,23 +652,6 @@ __device__ __forceinline__ void walk_conv_tile(const WalkGeom &g, float *out, do
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const long y0 = ty * CTH;
     walk_conv_columns<R, Shape>(g, out, w, weights, tx * 256 + wv * 64, lane, y0, y0 + CTH < g.rows ? y0 + CTH : g.rows);
-}
-
-// host: does `kernel` put ONE weight value on exactly the cells of the shape (zero elsewhere)?
-template <int R, typename Shape>
-inline bool is_uniform_shape(const double *kernel, double *weight) {
-    constexpr int K = 2 * R + 1;
-    const double w = kernel[R * K + R + Shape::hw(R, 0)];     // (the rim cell of the centre row: an annulus has no centre cell)
-    if (!(w != 0.0) || !std::isfinite(w)) return false;
-    for (int ky = 0; ky < K; ++ky) {
-        const int dy = ky < R ? R - ky : ky - R, h = Shape::hw(R, dy), hi = Shape::hwi(R, dy);
-        for (int kx = 0; kx < K; ++kx) {
-            const int dx = kx < R ? R - kx : kx - R;
-            if (kernel[ky * K + kx] != (dx <= h && dx > hi ? w : 0.0)) return false;
-        }
-    }
-    *weight = w;
-    return true;
 }
 
 // Nodata regions: is EVERY cell a wave's tile can see NaN (raster columns [x_lo, x_hi), rows [y_lo, y_hi), clipped to the

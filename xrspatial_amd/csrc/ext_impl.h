@@ -294,9 +294,8 @@ __global__ void __launch_bounds__(256, XRS_EXT_WAVES) focal_ext_kernel(const Ext
 }
 
 template <int R, typename Shape>
-int launch_ext(ExtArgs &a, const double *kernel, hipStream_t s) {
+int launch_ext(ExtArgs &a, hipStream_t s) {
     using C = ExtCfg<R, Shape>;
-    if (!is_shape<R, Shape>(kernel)) return -1;
     WalkGeom &g = a.g;
     g.tiles_x = (g.cols + 255) / 256;
     static thread_local int wg_per_cu = 0;                     // (per instantiation: registers depend on the radius)
@@ -313,23 +312,26 @@ int launch_ext(ExtArgs &a, const double *kernel, hipStream_t s) {
     return 0;
 }
 
+// the call's plane, geometry and max / min / range outputs; false: none of the three is wanted
+bool ext_args(ExtArgs &a, const WindowCall &c) {
+    memset(&a, 0, sizeof(a));
+    fill_geom(a.g, c);
+    a.out_max = c.out[XRS_STAT_MAX]; a.out_min = c.out[XRS_STAT_MIN]; a.out_range = c.out[XRS_STAT_RANGE];
+    return a.out_max || a.out_min || a.out_range;
+}
+
 }  // namespace
 
 namespace xrs {
 
 #ifndef XRS_EXT_ANNULUS_RMIN
 // 0 = launched, -1 = not this shape with a radius of 4..12 cells (caller takes another kernel), > 0 = error.
-int XRS_EXT_ENTRY(const float *in, float *out_max, float *out_min, float *out_range, long rows, long cols, long ld_in,
-                  long ld_out, const double *kernel, int krows, int kcols, int halo_top, int halo_bot, hipStream_t s) {
-    if (krows != kcols || !(krows & 1)) return -1;
-    if (!out_max && !out_min && !out_range) return 0;
+int XRS_EXT_ENTRY(const WindowCall &c) {
+    if (c.mask.kind != ShapeKind<XRS_EXT_SHAPE>::kind) return -1;
     ExtArgs a;
-    memset(&a, 0, sizeof(a));
-    a.g.in = in; a.g.rows = rows; a.g.cols = cols; a.g.ld_in = ld_in; a.g.ld_out = ld_out;
-    a.g.halo_top = halo_top; a.g.halo_bot = halo_bot;
-    a.out_max = out_max; a.out_min = out_min; a.out_range = out_range;
-    switch (krows / 2) {
-#define XRS_EXT_CASE(RR) case RR: return launch_ext<RR, XRS_EXT_SHAPE>(a, kernel, s);
+    if (!ext_args(a, c)) return 0;
+    switch (c.mask.R) {
+#define XRS_EXT_CASE(RR) case RR: return launch_ext<RR, XRS_EXT_SHAPE>(a, c.s);
         XRS_EXT_CASE(4) XRS_EXT_CASE(5) XRS_EXT_CASE(6) XRS_EXT_CASE(7) XRS_EXT_CASE(8) XRS_EXT_CASE(9) XRS_EXT_CASE(10) XRS_EXT_CASE(11)
         XRS_EXT_CASE(12)
 #undef XRS_EXT_CASE
@@ -340,35 +342,26 @@ int XRS_EXT_ENTRY(const float *in, float *out_max, float *out_min, float *out_ra
 // annulus_kernel(1, 1, R, RI) for XRS_EXT_ANNULUS_RMIN <= R <= XRS_EXT_ANNULUS_RMAX, 1 <= RI < R: one instantiation per pair.
 // 0 = launched, -1 = not such an annulus, > 0 = error.
 template <int RR, int RI>
-int ext_annulus_pair(ExtArgs &a, const double *kernel, int ri, hipStream_t s) {
+int ext_annulus_pair(ExtArgs &a, int ri, hipStream_t s) {
     if constexpr (RI >= RR) return -1;
     else {
-        if (ri == RI) return launch_ext<RR, AnnulusShape<RI>>(a, kernel, s);
-        return ext_annulus_pair<RR, RI + 1>(a, kernel, ri, s);
+        if (ri == RI) return launch_ext<RR, AnnulusShape<RI>>(a, s);
+        return ext_annulus_pair<RR, RI + 1>(a, ri, s);
     }
 }
 template <int RR>
-int ext_annulus_radius(ExtArgs &a, const double *kernel, int r, int ri, hipStream_t s) {
+int ext_annulus_radius(ExtArgs &a, int r, int ri, hipStream_t s) {
     if constexpr (RR > XRS_EXT_ANNULUS_RMAX) return -1;
     else {
-        if (r == RR) return ext_annulus_pair<RR, 1>(a, kernel, ri, s);
-        return ext_annulus_radius<RR + 1>(a, kernel, r, ri, s);
+        if (r == RR) return ext_annulus_pair<RR, 1>(a, ri, s);
+        return ext_annulus_radius<RR + 1>(a, r, ri, s);
     }
 }
-int XRS_EXT_ENTRY(const float *in, float *out_max, float *out_min, float *out_range, long rows, long cols, long ld_in,
-                  long ld_out, const double *kernel, int krows, int kcols, int halo_top, int halo_bot, hipStream_t s) {
-    if (krows != kcols || !(krows & 1)) return -1;
-    const int r = krows / 2;
-    if (r < XRS_EXT_ANNULUS_RMIN || r > XRS_EXT_ANNULUS_RMAX) return -1;
-    const int ri = annulus_inner_radius(kernel, krows);
-    if (ri < 1) return -1;
-    if (!out_max && !out_min && !out_range) return 0;
+int XRS_EXT_ENTRY(const WindowCall &c) {
+    if (c.mask.kind != WindowMask::ANNULUS || c.mask.R < XRS_EXT_ANNULUS_RMIN || c.mask.R > XRS_EXT_ANNULUS_RMAX) return -1;
     ExtArgs a;
-    memset(&a, 0, sizeof(a));
-    a.g.in = in; a.g.rows = rows; a.g.cols = cols; a.g.ld_in = ld_in; a.g.ld_out = ld_out;
-    a.g.halo_top = halo_top; a.g.halo_bot = halo_bot;
-    a.out_max = out_max; a.out_min = out_min; a.out_range = out_range;
-    return ext_annulus_radius<XRS_EXT_ANNULUS_RMIN>(a, kernel, r, ri, s);
+    if (!ext_args(a, c)) return 0;
+    return ext_annulus_radius<XRS_EXT_ANNULUS_RMIN>(a, c.mask.R, c.mask.RI, c.s);
 }
 #endif
 

@@ -17,6 +17,7 @@
 // float32 row-major for `sum` (Numba nansum keeps the array dtype).
 // No MFMA: 0/1 masks with NaN-skipping are not a dense contraction.
 #include "strip.h"
+#include "window_call.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -973,26 +974,77 @@ int launch_convolve_direct(KxkArgs a, hipStream_t s) {
     return 0;
 }
 
-// Column walkers (kxk_circle*.hip, kxk_box*.hip) for masks that are circles or boxes: -1 if neither.
-int try_walk_f32(const float *in, float *const *out, bool with_moments, long rows, long cols, long ld_in, long ld_out,
-                 const double *kernel, int krows, int kcols, int halo_top, int halo_bot, hipStream_t s) {
-    float *mean = with_moments ? out[XRS_STAT_MEAN] : nullptr, *var = with_moments ? out[XRS_STAT_VAR] : nullptr,
-          *sd = with_moments ? out[XRS_STAT_STD] : nullptr;
-    int rc = try_launch_focal_circle_f32(in, out[XRS_STAT_SUM], out[XRS_STAT_MAX], out[XRS_STAT_MIN], out[XRS_STAT_RANGE],
-                                         mean, var, sd, rows, cols, ld_in, ld_out, kernel, krows, kcols, halo_top, halo_bot, s);
-    if (rc < 0)
-        rc = try_launch_focal_box_f32(in, out[XRS_STAT_SUM], out[XRS_STAT_MAX], out[XRS_STAT_MIN], out[XRS_STAT_RANGE], mean,
-                                      var, sd, rows, cols, ld_in, ld_out, kernel, krows, kcols, halo_top, halo_bot, s);
-    return rc;
+// The mask of a call, recognised once: circle_kernel(R), np.ones((2R+1, 2R+1)), annulus_kernel(R, RI) or none of them, by the row
+// formulas the walkers are instantiated from (window_call.h).
+// `weighted` false -- focal statistics: a cell is on the shape if it is exactly 1 (focal.py:323) and off it with any other value.
+// `weighted` true -- convolve_2d: ONE finite non-zero weight on the shape's cells and exact zeros everywhere else.
+// The hole of an annulus is read off the centre row, from the centre to the first cell on the shape.  For focal statistics that
+// is "the first cell that is 1"; `hole_zero` says whether the cells before it are exact zeros, which is what the wide walker's
+// annulus units have always asked for (a focal mask with, say, 0.5 in its hole goes to the moments walker).  For convolve_2d
+// the two readings coincide: any non-zero cell before the first weight fails the mask anyway.
+WindowMask recognise_mask(const double *kernel, int krows, int kcols, bool weighted) {
+    WindowMask m = {WindowMask::OTHER, 0, -1, 1.0, false};
+    if (krows != kcols || krows < 3) return m;
+    const int K = krows, R = K / 2;
+    const double *mid = kernel + R * K + R;                  // the centre cell; its row is mid[-R .. R]
+    const double w = weighted ? mid[R] : 1.0;                // (the rim cell of the centre row is on all three shapes)
+    if (weighted && (!(w != 0.0) || !std::isfinite(w))) return m;
+    int ri = -1;
+    while (ri + 1 <= R && mid[ri + 1] != w) ++ri;
+    const WindowMask::Kind kind = kernel[0] == w ? WindowMask::BOX : ri < 0 ? WindowMask::CIRCLE : WindowMask::ANNULUS;
+    if (kind == WindowMask::ANNULUS && (ri < 1 || ri >= R)) return m;
+    for (int ky = 0; ky < K; ++ky) {
+        const int dy = ky < R ? R - ky : ky - R;
+        const int h = kind == WindowMask::BOX ? BoxShape::hw(R, dy) : CircleShape::hw(R, dy);
+        const int hi = kind == WindowMask::ANNULUS ? annulus_hole_hw(ri, dy) : -1;
+        for (int kx = 0; kx < K; ++kx) {
+            const int dx = kx < R ? R - kx : kx - R;
+            const double v = kernel[ky * K + kx];
+            if (dx <= h && dx > hi ? v != w : (v == w || (weighted && v != 0.0))) return m;
+        }
+    }
+    m.kind = kind; m.R = R; m.weight = w;
+    if (kind == WindowMask::ANNULUS) {
+        m.RI = ri;
+        m.hole_zero = true;
+        for (int dx = 0; dx <= ri; ++dx) m.hole_zero = m.hole_zero && mid[dx] == 0.0;
+    }
+    return m;
 }
-int try_walk_f64(const float *in, float *mean, float *var, float *sd, long rows, long cols, long ld_in, long ld_out,
-                 const double *kernel, int krows, int kcols, int halo_top, int halo_bot, hipStream_t s) {
-    int rc = try_launch_focal_circle_f64(in, mean, var, sd, rows, cols, ld_in, ld_out, kernel, krows, kcols, halo_top,
-                                         halo_bot, s);
-    if (rc < 0)
-        rc = try_launch_focal_box_f64(in, mean, var, sd, rows, cols, ld_in, ld_out, kernel, krows, kcols, halo_top, halo_bot, s);
-    return rc;
+
+// A walker family: the unit of the recognised shape (annuli: the unit that holds the outer radius, 4 .. 12).  -1: the mask
+// is no such shape, or the family has no unit for it; the unit itself answers -1 outside its range of radii.
+struct WalkerFamily {
+    WindowEntryFn *circle, *box;
+    WindowEntryFn *annulus[13];
+};
+int launch_by_shape(const WalkerFamily &f, const WindowCall &c) {
+    WindowEntryFn *entry = nullptr;
+    switch (c.mask.kind) {
+        case WindowMask::CIRCLE: entry = f.circle; break;
+        case WindowMask::BOX: entry = f.box; break;
+        case WindowMask::ANNULUS: entry = c.mask.R <= 12 ? f.annulus[c.mask.R] : nullptr; break;
+        case WindowMask::OTHER: break;
+    }
+    return entry ? entry(c) : -1;
 }
+const WalkerFamily walk_f32 = {try_launch_focal_circle_f32, try_launch_focal_box_f32, {}};     // column walkers: float32 statistics
+const WalkerFamily walk_f64 = {try_launch_focal_circle_f64, try_launch_focal_box_f64, {}};     // ... float64 moments
+const WalkerFamily strip_walk = {try_launch_focal_sw_circle, try_launch_focal_sw_box, {}};
+const WalkerFamily wide_walk = {try_launch_focal_wide_circle, try_launch_focal_wide_box,
+    {nullptr, nullptr, nullptr, nullptr, try_launch_wide_annulus4, try_launch_wide_annulus5, try_launch_wide_annulus6, try_launch_wide_annulus7,
+     try_launch_wide_annulus8, try_launch_wide_annulus9, try_launch_wide_annulus10, try_launch_wide_annulus11, try_launch_wide_annulus12}};
+const WalkerFamily wide_conv = {try_launch_conv_wide_circle, try_launch_conv_wide_box,           // (the annulus units serve both)
+    {nullptr, nullptr, nullptr, nullptr, try_launch_wide_annulus4, try_launch_wide_annulus5, try_launch_wide_annulus6, try_launch_wide_annulus7,
+     try_launch_wide_annulus8, try_launch_wide_annulus9, try_launch_wide_annulus10, try_launch_wide_annulus11, try_launch_wide_annulus12}};
+const WalkerFamily ext_walk = {try_launch_focal_ext_circle, try_launch_focal_ext_box,
+    {nullptr, nullptr, nullptr, nullptr, try_launch_focal_ext_annulus_a, try_launch_focal_ext_annulus_a, try_launch_focal_ext_annulus_a,
+     try_launch_focal_ext_annulus_a, try_launch_focal_ext_annulus_a, try_launch_focal_ext_annulus_a, try_launch_focal_ext_annulus_b,
+     try_launch_focal_ext_annulus_b, try_launch_focal_ext_annulus_c}};
+const WalkerFamily mom_walk = {try_launch_focal_mom_circle, try_launch_focal_mom_box,
+    {nullptr, nullptr, nullptr, nullptr, try_launch_focal_mom_annulus4, try_launch_focal_mom_annulus5, try_launch_focal_mom_annulus6,
+     try_launch_focal_mom_annulus7, try_launch_focal_mom_annulus8, try_launch_focal_mom_annulus9, try_launch_focal_mom_annulus10,
+     try_launch_focal_mom_annulus11, try_launch_focal_mom_annulus12}};
 
 template <bool MEAN_ONLY>
 int dispatch_focal(const KxkArgs &a, bool vec, size_t lds, hipStream_t s) {
@@ -1004,30 +1056,6 @@ int dispatch_focal(const KxkArgs &a, bool vec, size_t lds, hipStream_t s) {
     return launch_focal<0, 0, MEAN_ONLY ? 0 : 1>(a, vec, lds, s);
 }
 
-// mean / var / std / sum over annulus_kernel(1, 1, R, RI): the moments walker's translation unit for the outer radius
-int launch_mom_annulus(const float *in, float *o_sum, float *o_mean, float *o_var, float *o_std, long rows, long cols, long ld_in,
-                       long ld_out, const double *kernel, int krows, int kcols, int ht, int hb, hipStream_t s) {
-    if (krows != kcols) return -1;
-    switch (krows / 2) {
-#define XRS_ANN(RR) case RR: return try_launch_focal_mom_annulus##RR(in, o_sum, o_mean, o_var, o_std, rows, cols, ld_in, ld_out, kernel, krows, kcols, ht, hb, s);
-        XRS_ANN(4) XRS_ANN(5) XRS_ANN(6) XRS_ANN(7) XRS_ANN(8) XRS_ANN(9) XRS_ANN(10) XRS_ANN(11) XRS_ANN(12)
-#undef XRS_ANN
-        default: return -1;
-    }
-}
-
-// the mean or the uniform-weight convolution over annulus_kernel(1, 1, R, RI): the wide walker's translation unit for the outer radius
-int launch_wide_annulus(const float *in, float *o_mean, float *o_conv, long rows, long cols, long ld_in, long ld_out,
-                        const double *kernel, const double *weights_dev, int krows, int kcols, int ht, int hb, hipStream_t s) {
-    if (krows != kcols) return -1;
-    switch (krows / 2) {
-#define XRS_ANN(RR) case RR: return try_launch_wide_annulus##RR(in, o_mean, o_conv, rows, cols, ld_in, ld_out, kernel, weights_dev, krows, kcols, ht, hb, s);
-        XRS_ANN(4) XRS_ANN(5) XRS_ANN(6) XRS_ANN(7) XRS_ANN(8) XRS_ANN(9) XRS_ANN(10) XRS_ANN(11) XRS_ANN(12)
-#undef XRS_ANN
-        default: return -1;
-    }
-}
-
 }  // namespace
 
 extern "C" {
@@ -1037,13 +1065,11 @@ size_t xrs_kxk_workspace_bytes(int krows, int kcols) {
     return (size_t)krows * kcols * sizeof(double);       // float64 weights of convolve2d
 }
 
-// the kernel copy (256-byte aligned) + the tile map of the separable box walk (boxsep.hip) + the work-list of the moments
-// kernels' slow tiles (mom_impl.h: focal_mom_rescue_kernel)
-static size_t weights_span(int krows, int kcols) { return ((size_t)krows * kcols * sizeof(double) + 255) & ~(size_t)255; }
-static size_t todo_span(long rows, long cols) { return (box_todo_bytes(rows, cols) + 255) & ~(size_t)255; }
+// the kernel copy, the tile map of the separable box walk, the work-list of the moments / wide kernels' slow tiles and the
+// band list behind it: workspace_layout (window_call.h)
 size_t xrs_focal_workspace_bytes(int64_t rows, int64_t cols, int krows, int kcols) {
     if (krows <= 0 || kcols <= 0 || rows < 0 || cols < 0) return 0;
-    return weights_span(krows, kcols) + todo_span(rows, cols) + mom_rescue_bytes(rows, cols);
+    return workspace_layout(rows, cols, krows, kcols).bytes;
 }
 
 int xrs_convolve2d_f32(const float *in_dev, float *out_dev, int64_t rows, int64_t cols, int64_t ld_in,
@@ -1068,17 +1094,16 @@ int xrs_convolve2d_f32(const float *in_dev, float *out_dev, int64_t rows, int64_
     hipStream_t s = as_stream(stream);
     XRS_HIP(hipMemcpyAsync(work_dev, kernel, (size_t)krows * kcols * sizeof(double), hipMemcpyHostToDevice, s));
     a.weights = static_cast<const double *>(work_dev);
-    if (krows >= 7) {
-        // one weight value on a circle / box (normalised circle_kernel, np.ones / k^2): the wide row walker (wide_impl.h,
-        // float32 on shifted values, guarded)
-        int rc = -1;
-        rc = try_launch_conv_wide_circle(in_dev, out_dev, rows, cols, ld_in, ld_out, kernel, a.weights, krows, kcols, halo_top, halo_bot, s);
-        if (rc < 0)
-            rc = try_launch_conv_wide_box(in_dev, out_dev, rows, cols, ld_in, ld_out, kernel, a.weights, krows, kcols, halo_top, halo_bot, s);
-        if (rc < 0)             // a normalised annulus_kernel (focal.hotspots' other documented mask)
-            rc = launch_wide_annulus(in_dev, nullptr, out_dev, rows, cols, ld_in, ld_out, kernel, a.weights, krows, kcols, halo_top, halo_bot, s);
-        if (rc >= 0) return rc;
-    }
+    // one weight value on a circle / box / annulus of radius 3 (annulus: 4) .. 12 (normalised circle_kernel, np.ones / k^2,
+    // annulus_kernel -- focal.hotspots' documented masks): the wide row walker (wide_impl.h, float32 on shifted values, guarded);
+    // anything else: the tap kernels below
+    WindowCall c;
+    memset(&c, 0, sizeof(c));
+    c.in = in_dev; c.rows = rows; c.cols = cols; c.ld_in = ld_in; c.ld_out = ld_out; c.halo_top = halo_top; c.halo_bot = halo_bot;
+    c.out_conv = out_dev; c.weights_dev = a.weights;
+    c.kernel = kernel; c.krows = krows; c.kcols = kcols; c.s = s;
+    c.mask = recognise_mask(kernel, krows, kcols, true);
+    if (const int rc = launch_by_shape(wide_conv, c); rc >= 0) return rc;
     a.tiles_x = (cols + TW - 1) / TW;
     a.n_tiles = a.tiles_x * ((rows + a.th - 1) / a.th);
     if (krows == 3 && kcols == 3) return launch_convolve_direct<3, 3>(a, s);
@@ -1099,6 +1124,30 @@ int xrs_focal_stats_f32(const float *in_dev, float *const *outs_dev, unsigned st
                                   work_dev ? xrs_kxk_workspace_bytes(krows, kcols) : 0, halo_top, halo_bot, 0u, stream);
 }
 
+// Which kernels a call launches.  Mask kinds: C circle, B box, A annulus (recognise_mask; radius R, K = 2R + 1), any = whatever
+// is left, other shapes included.  Rows are tried top to bottom; a walker outside its range of radii, and a run kernel whose mask
+// does not suit it, passes the call on to the rows below.  EXACT = XRS_FOCAL_EXACT_MOMENTS, SEQ = XRS_FOCAL_SEQUENTIAL_SUM.
+//
+//   mask        statistics                      flags        kernels
+//   K > 63      any                             any          kxk_big
+//   C B  3-12   mean and / or sum               no EXACT,    wide walker (one launch per plane)
+//   A    4-12   mean                            no SEQ with  wide walker (hole of exact zeros), else moments walker
+//   A    4-12   sum, mean + sum                 a sum        moments walker
+//   C B A 4-12  anything beyond mean / sum      no EXACT     extrema walker (max / min / range) + moments walker (the rest; B with
+//                                                            a workspace: boxsep in front); SEQ: the sum from the f32 column walker
+//   C B  3-12   mean                            (EXACT)      f64 column walker
+//   any K*K>49  mean                                         prefix-sum run kernel
+//   any K*K>49  several                                      mean / var / std: f64 column walker (C B 2-12), else run kernel;
+//                                                            sum / max / min / range: f32 column walker (C B), else LDS-tile tap walk
+//   5x5 C, 3x3 B  mean                                       raster pass (pass.hip) without terrain products
+//   any         mean                                         3x3, 5x5: register strips; 7x7: fast LDS tile; else LDS-tile tap walk
+//   C B  2-3    with mean / var / std           no EXACT,    strip walker (sw_impl.h)
+//                                               no SEQ sum
+//   C B  2-3    several                                      with sum / max / min / range: f32 column walker (all seven); else f64
+//   any         several                                      3x3, 5x5: register strips; else LDS-tile tap walk
+//
+// The work-list of the moments and wide walkers, the band list and boxsep's tile map exist when the caller's workspace holds
+// xrs_focal_workspace_bytes(); with less (xrs_kxk_workspace_bytes, or none) slow tiles are walked in place and boxsep is not run.
 int xrs_focal_stats_f32_ex(const float *in_dev, float *const *outs_dev, unsigned stat_mask, int64_t rows,
                            int64_t cols, int64_t ld_in, int64_t ld_out, const double *kernel, int krows,
                            int kcols, void *work_dev, size_t work_bytes, int halo_top, int halo_bot, unsigned flags,
@@ -1108,114 +1157,82 @@ int xrs_focal_stats_f32_ex(const float *in_dev, float *const *outs_dev, unsigned
     if (!outs_dev) return fail("xrs_focal_stats_f32: null outputs");
     stat_mask &= (1u << XRS_NUM_STATS) - 1;
     if (!stat_mask) return 0;
-    KxkArgs a;
-    memset(&a, 0, sizeof(a));
-    a.in = in_dev;
+    WindowCall c;
+    memset(&c, 0, sizeof(c));
+    c.in = in_dev; c.rows = rows; c.cols = cols; c.ld_in = ld_in; c.ld_out = ld_out; c.halo_top = halo_top; c.halo_bot = halo_bot;
+    c.kernel = kernel; c.krows = krows; c.kcols = kcols; c.s = as_stream(stream);
     for (int i = 0; i < XRS_NUM_STATS; ++i) {
         if (stat_mask >> i & 1) {
             if (!outs_dev[i]) return fail("xrs_focal_stats_f32: statistic %d selected but its output is NULL", i);
-            a.out[i] = outs_dev[i];
+            c.out[i] = outs_dev[i];
         }
     }
     if (rows == 0 || cols == 0) return 0;
-    hipStream_t s = as_stream(stream);
+    hipStream_t s = c.s;
     if (krows > MAX_K || kcols > MAX_K) {
         if (!work_dev || work_bytes < xrs_kxk_workspace_bytes(krows, kcols)) return fail("xrs_focal_stats_f32: windows beyond 63x63 need a workspace of xrs_kxk_workspace_bytes()");
-        return launch_window_any_size(false, in_dev, a.out, rows, cols, ld_in, ld_out, kernel, krows, kcols, work_dev, halo_top,
+        return launch_window_any_size(false, in_dev, c.out, rows, cols, ld_in, ld_out, kernel, krows, kcols, work_dev, halo_top,
                                       halo_bot, s);
     }
-    // np.ones((k, k)): scratch for the tile map of the separable walk (boxsep.hip), if the caller brought enough
-    const bool have_work = work_dev && work_bytes >= xrs_focal_workspace_bytes(rows, cols, krows, kcols);
-    unsigned char *const box_todo = have_work ? static_cast<unsigned char *>(work_dev) + weights_span(krows, kcols) : nullptr;
-    // ... and for the work-list of the moments kernels (mom_impl.h); without it their slow tiles are walked in place
-    struct RescueScope {
-        explicit RescueScope(unsigned *p) { mom_rescue_slot() = p; }
-        ~RescueScope() { mom_rescue_slot() = nullptr; }
-    } rescue_scope(have_work ? reinterpret_cast<unsigned *>(static_cast<unsigned char *>(work_dev) + weights_span(krows, kcols) + todo_span(rows, cols))
-                             : nullptr);
-    // Large circles / boxes: the float32 walkers of wide_impl.h / ext_impl.h / mom_impl.h.  XRS_FOCAL_EXACT_MOMENTS keeps
-    // the float64 column walkers (mean / var / std within ~1 ulp of the reference's float64 accumulators, ~2x the time);
-    // XRS_FOCAL_SEQUENTIAL_SUM keeps `sum` on the kernel that adds the taps in the reference's order in float32 (bit-exact
-    // with numba's nansum) instead of rounding the exact sum once.
+    const WorkspaceLayout w = workspace_layout(rows, cols, krows, kcols);
+    if (work_dev && work_bytes >= w.bytes) {
+        unsigned char *const base = static_cast<unsigned char *>(work_dev);
+        c.box_todo = base + w.todo_off;
+        c.worklist = reinterpret_cast<unsigned *>(base + w.worklist_off);
+        c.worklist_bytes = w.worklist_bytes;
+        c.exact = reinterpret_cast<unsigned *>(base + w.exact_off);
+        c.exact_cap = w.exact_cap;
+    }
+    // XRS_FOCAL_EXACT_MOMENTS keeps the float64 column walkers (mean / var / std within ~1 ulp of the reference's float64
+    // accumulators, ~2x the time); XRS_FOCAL_SEQUENTIAL_SUM keeps `sum` on the kernel that adds the taps in the reference's order in
+    // float32 (bit-exact with numba's nansum) instead of rounding the exact sum once.
     if (flags & ~(unsigned)(XRS_FOCAL_EXACT_MOMENTS | XRS_FOCAL_SEQUENTIAL_SUM)) return fail("xrs_focal_stats_f32_ex: unknown flag bits 0x%x", flags);
     const bool gen1 = (flags & XRS_FOCAL_EXACT_MOMENTS) != 0;
     const bool seq_sum = (flags & XRS_FOCAL_SEQUENTIAL_SUM) != 0;
     const unsigned m_mean = 1u << XRS_STAT_MEAN, m_sum = 1u << XRS_STAT_SUM;
-    if (!gen1 && krows == kcols && krows >= 7 && !(stat_mask & ~(m_mean | m_sum)) && !((stat_mask & m_sum) && seq_sum)) {
-        // mean and / or sum only: one 16-byte load per lane and row, float32 prefix sums (wide_impl.h)
-        int rc = try_launch_focal_wide_circle(in_dev, a.out[XRS_STAT_MEAN], a.out[XRS_STAT_SUM], rows, cols, ld_in, ld_out,
-                                              kernel, krows, kcols, halo_top, halo_bot, s);
-        if (rc < 0)
-            rc = try_launch_focal_wide_box(in_dev, a.out[XRS_STAT_MEAN], a.out[XRS_STAT_SUM], rows, cols, ld_in, ld_out,
-                                           kernel, krows, kcols, halo_top, halo_bot, s);
-        // annulus_kernel(1, 1, R, RI), the mean alone: the wide walker's annulus instantiations (a row with a hole = two runs)
-        if (rc < 0 && stat_mask == m_mean)
-            rc = launch_wide_annulus(in_dev, a.out[XRS_STAT_MEAN], nullptr, rows, cols, ld_in, ld_out, kernel, nullptr, krows, kcols,
-                                     halo_top, halo_bot, s);
-        // ... with the sum: the moments walker with only the mean / sum planes
-        if (rc < 0 && krows >= 9)
-            rc = launch_mom_annulus(in_dev, a.out[XRS_STAT_SUM], a.out[XRS_STAT_MEAN], nullptr, nullptr, rows, cols, ld_in, ld_out, kernel,
-                                    krows, kcols, halo_top, halo_bot, s);
+    const unsigned f64_stats = m_mean | (1u << XRS_STAT_VAR) | (1u << XRS_STAT_STD);
+    const unsigned mm_stats = (1u << XRS_STAT_MAX) | (1u << XRS_STAT_MIN) | (1u << XRS_STAT_RANGE);
+    c.mask = recognise_mask(kernel, krows, kcols, false);
+    if (!gen1 && !(stat_mask & ~(m_mean | m_sum)) && !((stat_mask & m_sum) && seq_sum)) {
+        // mean and / or sum only: one 16-byte load per lane and row, float32 prefix sums (wide_impl.h).  Annuli: the wide walker
+        // has the mean alone (a row with a hole = two runs); with the sum, the moments walker with only those planes
+        int rc = -1;
+        if (c.mask.kind != WindowMask::ANNULUS || stat_mask == m_mean) rc = launch_by_shape(wide_walk, c);
+        if (rc < 0 && c.mask.kind == WindowMask::ANNULUS) rc = launch_by_shape(mom_walk, c);
         if (rc >= 0) return rc;
     }
-    if (!gen1 && krows == kcols && krows >= 9 && (stat_mask & ~(m_mean | m_sum))) {
-        // several statistics on a circle / box: the extrema walker (ext_impl.h: max / min / range) and the moments walker
-        // (mom_impl.h: mean / var / std / sum), each one pass; a sequential `sum` comes from its own kernel.
-        float *o_sum = seq_sum ? nullptr : a.out[XRS_STAT_SUM];
-        const bool want_mm = a.out[XRS_STAT_MAX] || a.out[XRS_STAT_MIN] || a.out[XRS_STAT_RANGE];
-        const bool want_mom = o_sum || a.out[XRS_STAT_MEAN] || a.out[XRS_STAT_VAR] || a.out[XRS_STAT_STD];
-        {
-            hipStream_t s_mm = s;          // (the two launches on two streams, forked / joined by events, measured no faster than back to back:
-                                           //  2.39 vs 2.43 ms in round 3; 2.14 - 2.23 vs 2.19 in round 4, also with the extrema kernel at 2 waves per SIMD:
-                                           //  profiles/r04/ab_two_streams.log)
-            int rc = 0;
-            if (want_mm) {
-                rc = try_launch_focal_ext_circle(in_dev, a.out[XRS_STAT_MAX], a.out[XRS_STAT_MIN], a.out[XRS_STAT_RANGE], rows,
-                                                 cols, ld_in, ld_out, kernel, krows, kcols, halo_top, halo_bot, s_mm);
-                if (rc < 0)
-                    rc = try_launch_focal_ext_box(in_dev, a.out[XRS_STAT_MAX], a.out[XRS_STAT_MIN], a.out[XRS_STAT_RANGE], rows,
-                                                  cols, ld_in, ld_out, kernel, krows, kcols, halo_top, halo_bot, s_mm);
-                // annulus_kernel(1, 1, R, RI): the same walkers, one instantiation per radius pair
-                typedef int (*ExtFn)(const float *, float *, float *, float *, long, long, long, long, const double *, int, int, int, int, hipStream_t);
-                const ExtFn ann[3] = {try_launch_focal_ext_annulus_a, try_launch_focal_ext_annulus_b, try_launch_focal_ext_annulus_c};
-                for (int i = 0; i < 3 && rc < 0; ++i)
-                    rc = ann[i](in_dev, a.out[XRS_STAT_MAX], a.out[XRS_STAT_MIN], a.out[XRS_STAT_RANGE], rows, cols, ld_in, ld_out, kernel,
-                                krows, kcols, halo_top, halo_bot, s_mm);
-            }
-            if (rc == 0 && want_mom) {
-                rc = try_launch_focal_mom_circle(in_dev, o_sum, a.out[XRS_STAT_MEAN], a.out[XRS_STAT_VAR], a.out[XRS_STAT_STD],
-                                                 rows, cols, ld_in, ld_out, kernel, krows, kcols, halo_top, halo_bot, s);
-                if (rc < 0)
-                    rc = try_launch_focal_mom_box(in_dev, o_sum, a.out[XRS_STAT_MEAN], a.out[XRS_STAT_VAR], a.out[XRS_STAT_STD],
-                                                  rows, cols, ld_in, ld_out, kernel, krows, kcols, halo_top, halo_bot, s, box_todo);
-                if (rc < 0) rc = launch_mom_annulus(in_dev, o_sum, a.out[XRS_STAT_MEAN], a.out[XRS_STAT_VAR], a.out[XRS_STAT_STD], rows, cols,
-                                                    ld_in, ld_out, kernel, krows, kcols, halo_top, halo_bot, s);
-            }
-            if (rc > 0) return rc;
-            if (rc == 0) {
-                if (!(seq_sum && a.out[XRS_STAT_SUM])) return 0;
-                float *only_sum[XRS_NUM_STATS] = {nullptr};
-                only_sum[XRS_STAT_SUM] = a.out[XRS_STAT_SUM];
-                const int rc2 = try_walk_f32(in_dev, only_sum, false, rows, cols, ld_in, ld_out, kernel, krows, kcols, halo_top,
-                                             halo_bot, s);
-                if (rc2 >= 0) return rc2;
-                return fail("xrs_focal_stats_f32: no sequential-sum kernel for this mask");
-            }
-            // (rc < 0: neither a circle nor a box of radius 4..12 -- the kernels below)
+    if (!gen1 && (stat_mask & ~(m_mean | m_sum))) {
+        // several statistics: the extrema walker (ext_impl.h: max / min / range) and the moments walker (mom_impl.h: mean /
+        // var / std / sum), each one pass, back to back on the one stream (two streams, forked / joined by events, measured no
+        // faster: 2.39 vs 2.43 ms in round 3; 2.14 - 2.23 vs 2.19 in round 4: profiles/r04/ab_two_streams.log); a sequential
+        // `sum` comes from its own kernel.
+        const WindowCall c_mom = seq_sum ? with_outputs(c, ~m_sum) : c;
+        int rc = 0;
+        if (stat_mask & mm_stats) rc = launch_by_shape(ext_walk, c);
+        if (rc == 0 && (c_mom.out[XRS_STAT_SUM] || (stat_mask & f64_stats))) rc = launch_by_shape(mom_walk, c_mom);
+        if (rc > 0) return rc;
+        if (rc == 0) {
+            if (!(seq_sum && c.out[XRS_STAT_SUM])) return 0;
+            const int rc2 = launch_by_shape(walk_f32, with_outputs(c, m_sum));
+            if (rc2 >= 0) return rc2;
+            return fail("xrs_focal_stats_f32: no sequential-sum kernel for this mask");
         }
+        // (rc < 0: no circle, box or annulus of radius 4..12 -- the kernels below)
     }
-    if (stat_mask == (1u << XRS_STAT_MEAN) && krows * kcols >= 49) {
+    if (stat_mask == m_mean && krows * kcols >= 49) {
         // circles and boxes, 7x7 .. 25x25: column walker (running float64 sums over centred runs)
-        const int rc = try_walk_f64(in_dev, a.out[XRS_STAT_MEAN], nullptr, nullptr, rows, cols, ld_in, ld_out, kernel,
-                                    krows, kcols, halo_top, halo_bot, s);
+        const int rc = launch_by_shape(walk_f64, c);
         if (rc >= 0) return rc;
     }
-    if (stat_mask == (1u << XRS_STAT_MEAN) && krows * kcols > 49) {
+    if (stat_mask == m_mean && krows * kcols > 49) {
         // large run-structured masks (circles, boxes, annuli): prefix-sum kernel, O(rows of the mask) per cell
-        const int rc = try_launch_focal_mean_runs(in_dev, a.out[XRS_STAT_MEAN], rows, cols, ld_in, ld_out, kernel,
-                                                  krows, kcols, halo_top, halo_bot, s);
+        const int rc = try_launch_focal_mean_runs(c);
         if (rc >= 0) return rc;
     }
+    KxkArgs a;
+    memset(&a, 0, sizeof(a));
+    a.in = in_dev;
+    for (int i = 0; i < XRS_NUM_STATS; ++i) a.out[i] = c.out[i];
     a.rows = rows; a.cols = cols; a.ld_in = ld_in; a.ld_out = ld_out;
     a.halo_top = halo_top; a.halo_bot = halo_bot; a.krows = krows; a.kcols = kcols;
     size_t lds;
@@ -1230,59 +1247,44 @@ int xrs_focal_stats_f32_ex(const float *in_dev, float *const *outs_dev, unsigned
         a.ntaps += __builtin_popcountll(bits);
     }
     a.inv_ntaps = a.ntaps ? 1.0 / a.ntaps : 0.0;
-    (void)work_dev;   // reserved (row-run tables for large masks); the bit-rows travel as kernel arguments
 
     a.tiles_x = (cols + TW - 1) / TW;
     a.n_tiles = a.tiles_x * ((rows + a.th - 1) / a.th);
     const bool vec = vec_ok(a, stat_mask);
-    if (stat_mask != (1u << XRS_STAT_MEAN) && krows * kcols > 49) {
-        // large run-structured masks, several statistics: mean / var / std from prefix sums (kxk_runs.hip),
-        // the float32 statistics (row-major sum, min, max, range) from one tap walk over the LDS tile
-        const unsigned f64_stats = (1u << XRS_STAT_MEAN) | (1u << XRS_STAT_VAR) | (1u << XRS_STAT_STD);
+    if (stat_mask != m_mean && krows * kcols > 49) {
+        // large run-structured masks, several statistics: mean / var / std from the float64 column walker (circles, boxes) or
+        // from prefix sums (kxk_runs.hip); the float32 statistics (row-major sum, min, max, range) from the float32 column
+        // walker (kxk_circle.hip / kxk_box.hip) or from one tap walk over the LDS tile
         int rc = 0;
         if (stat_mask & f64_stats) {
-            rc = try_walk_f64(in_dev, a.out[XRS_STAT_MEAN], a.out[XRS_STAT_VAR], a.out[XRS_STAT_STD], rows, cols, ld_in, ld_out,
-                              kernel, krows, kcols, halo_top, halo_bot, s);
+            rc = launch_by_shape(walk_f64, c);
+            if (rc < 0) rc = try_launch_focal_meanvar_runs(c);
             if (rc > 0) return rc;
         }
-        if ((stat_mask & f64_stats) && rc < 0)
-            rc = try_launch_focal_meanvar_runs(in_dev, a.out[XRS_STAT_MEAN], a.out[XRS_STAT_VAR], a.out[XRS_STAT_STD], rows,
-                                               cols, ld_in, ld_out, kernel, krows, kcols, halo_top, halo_bot, s);
-        if (rc > 0) return rc;
         if (rc == 0) {
             if (!(stat_mask & ~f64_stats)) return 0;
-            // circles and boxes: column walker (kxk_circle.hip / kxk_box.hip); any other run-structured mask: tap walk
-            const int rc2 = try_walk_f32(in_dev, a.out, false, rows, cols, ld_in, ld_out, kernel, krows, kcols, halo_top,
-                                         halo_bot, s);
+            const int rc2 = launch_by_shape(walk_f32, with_outputs(c, ~f64_stats));
             if (rc2 >= 0) return rc2;
-            const bool want_sum = stat_mask >> XRS_STAT_SUM & 1;
-            const bool want_mm = stat_mask & ((1u << XRS_STAT_MAX) | (1u << XRS_STAT_MIN) | (1u << XRS_STAT_RANGE));
-            if (!want_mm) return launch_focal<0, 0, 3>(a, vec, lds, s);
-            if (!want_sum) return launch_focal<0, 0, 4>(a, vec, lds, s);
+            if (!(stat_mask & mm_stats)) return launch_focal<0, 0, 3>(a, vec, lds, s);
+            if (!(stat_mask & m_sum)) return launch_focal<0, 0, 4>(a, vec, lds, s);
             return launch_focal<0, 0, 2>(a, vec, lds, s);
         }
     }
-    if (stat_mask == (1u << XRS_STAT_MEAN) && pass_has_compile_time_mask(kernel, krows, kcols)) {
+    if (stat_mask == m_mean && pass_has_compile_time_mask(kernel, krows, kcols)) {
         // circle_kernel(1, 1, 2) / np.ones((3, 3)): the strip kernel of pass.hip without terrain products -- compile-time
         // mask, shared row sums
         return xrs_raster_pass_f32(in_dev, nullptr, nullptr, nullptr, nullptr, a.out[XRS_STAT_MEAN], kernel, krows, kcols, work_dev,
                                    rows, cols, ld_in, ld_out, 1.0, 1.0, 0.0, 0.0, halo_top, halo_bot, stream);
     }
-    if (stat_mask == (1u << XRS_STAT_MEAN)) return dispatch_focal<true>(a, vec, lds, s);
-    if ((krows == 5 || krows == 7) && krows == kcols && !gen1 && !(seq_sum && a.out[XRS_STAT_SUM]) &&
-        (a.out[XRS_STAT_VAR] || a.out[XRS_STAT_STD] || a.out[XRS_STAT_MEAN])) {
-        // small circles / boxes with moments among the statistics: everything from one pass of the strip walker (sw_impl.h)
-        int rc = try_launch_focal_sw_circle(in_dev, a.out, rows, cols, ld_in, ld_out, kernel, krows, kcols, halo_top, halo_bot, s);
-        if (rc < 0) rc = try_launch_focal_sw_box(in_dev, a.out, rows, cols, ld_in, ld_out, kernel, krows, kcols, halo_top, halo_bot, s);
-        if (rc >= 0) return rc;
-    }
-    if (krows <= 7 && krows == kcols && krows >= 5) {
-        // small circles / boxes (5x5, 7x7): all requested statistics from one column-walker kernel
-        const bool f32_stats = a.out[XRS_STAT_SUM] || a.out[XRS_STAT_MAX] || a.out[XRS_STAT_MIN] || a.out[XRS_STAT_RANGE];
-        const int rc = f32_stats
-            ? try_walk_f32(in_dev, a.out, true, rows, cols, ld_in, ld_out, kernel, krows, kcols, halo_top, halo_bot, s)
-            : try_walk_f64(in_dev, a.out[XRS_STAT_MEAN], a.out[XRS_STAT_VAR], a.out[XRS_STAT_STD], rows, cols, ld_in,
-                           ld_out, kernel, krows, kcols, halo_top, halo_bot, s);
+    if (stat_mask == m_mean) return dispatch_focal<true>(a, vec, lds, s);
+    if (c.mask.R == 2 || c.mask.R == 3) {
+        // small circles / boxes (5x5, 7x7).  With moments among the statistics: everything from one pass of the strip walker
+        // (sw_impl.h).  Under EXACT, or a sequential sum, or without moments: one column-walker kernel for all of them
+        if (!gen1 && !(seq_sum && c.out[XRS_STAT_SUM]) && (stat_mask & f64_stats)) {
+            const int rc = launch_by_shape(strip_walk, c);
+            if (rc >= 0) return rc;
+        }
+        const int rc = launch_by_shape((stat_mask & ~f64_stats) ? walk_f32 : walk_f64, c);
         if (rc >= 0) return rc;
     }
     // the all-statistics kernel always produces the mean internally; give it somewhere to go

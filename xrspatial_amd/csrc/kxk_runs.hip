@@ -15,7 +15,7 @@
 //                sum += P[row][x + e] - P[row][x + s] for every run (row, s, e) of the mask.
 // Tiles that contain +-inf (prefix differences would give inf - inf) fall back to a direct tap loop
 // over global memory for that tile only.
-#include "xrs_common.h"
+#include "window_call.h"
 
 #include <cmath>
 
@@ -401,27 +401,19 @@ int launch_runs(K kernel_fn, RunArgs &a, size_t bytes_per_cell, hipStream_t s) {
 namespace xrs {
 
 // Both return 0 if launched, -1 if the mask does not fit the kernel (caller falls back), > 0 on error.
-int try_launch_focal_mean_runs(const float *in, float *out, long rows, long cols, long ld_in, long ld_out,
-                               const double *kernel, int krows, int kcols, int halo_top, int halo_bot,
-                               hipStream_t s) {
+static int launch_runs_for(const WindowCall &c, bool with_var) {
     RunArgs a;
     memset(&a, 0, sizeof(a));
-    if (!parse_runs(a, kernel, krows, kcols)) return -1;
-    a.in = in; a.out = out; a.rows = rows; a.cols = cols; a.ld_in = ld_in; a.ld_out = ld_out;
-    a.halo_top = halo_top; a.halo_bot = halo_bot;
-    return launch_runs(focal_mean_runs_kernel, a, sizeof(double) + sizeof(int), s);
+    if (!parse_runs(a, c.kernel, c.krows, c.kcols)) return -1;
+    a.in = c.in; a.out = c.out[XRS_STAT_MEAN];
+    if (with_var) { a.out_var = c.out[XRS_STAT_VAR]; a.out_std = c.out[XRS_STAT_STD]; }
+    a.rows = c.rows; a.cols = c.cols; a.ld_in = c.ld_in; a.ld_out = c.ld_out;
+    a.halo_top = c.halo_top; a.halo_bot = c.halo_bot;
+    if (with_var) return launch_runs(focal_meanvar_runs_kernel, a, 2 * sizeof(double) + sizeof(int), c.s);
+    return launch_runs(focal_mean_runs_kernel, a, sizeof(double) + sizeof(int), c.s);
 }
-
-int try_launch_focal_meanvar_runs(const float *in, float *out_mean, float *out_var, float *out_std, long rows,
-                                  long cols, long ld_in, long ld_out, const double *kernel, int krows, int kcols,
-                                  int halo_top, int halo_bot, hipStream_t s) {
-    RunArgs a;
-    memset(&a, 0, sizeof(a));
-    if (!parse_runs(a, kernel, krows, kcols)) return -1;
-    a.in = in; a.out = out_mean; a.out_var = out_var; a.out_std = out_std;
-    a.rows = rows; a.cols = cols; a.ld_in = ld_in; a.ld_out = ld_out;
-    a.halo_top = halo_top; a.halo_bot = halo_bot;
-    return launch_runs(focal_meanvar_runs_kernel, a, 2 * sizeof(double) + sizeof(int), s);
-}
+int try_launch_focal_mean_runs(const WindowCall &c) { return launch_runs_for(c, false); }
+// same tiles, plus variance / standard deviation from a second prefix array (any output may be null)
+int try_launch_focal_meanvar_runs(const WindowCall &c) { return launch_runs_for(c, true); }
 
 }  // namespace xrs

@@ -800,9 +800,9 @@ __global__ void __launch_bounds__(256) focal_mom_exact_kernel(const MomArgs a) {
 }
 
 template <int R, typename Shape>
-int launch_mom(MomArgs &a, const double *kernel, hipStream_t s) {
+int launch_mom(MomArgs &a, const WindowCall &c) {
     using C = MomCfg<R, Shape>;
-    if (!is_shape<R, Shape>(kernel)) return -1;
+    hipStream_t s = c.s;
     WalkGeom &g = a.g;
     g.tiles_x = (g.cols + C::TW - 1) / C::TW;
     static thread_local int wg_per_cu = 0;                     // (per instantiation: registers depend on the radius)
@@ -826,14 +826,14 @@ int launch_mom(MomArgs &a, const double *kernel, hipStream_t s) {
     }
     const int om = (a.out_sum ? MOM_SUM : 0) | (a.out_mean ? MOM_MEAN : 0) | (a.out_var ? MOM_VAR : 0) | (a.out_std ? MOM_STD : 0);
     constexpr int ALL = MOM_SUM | MOM_MEAN | MOM_VAR | MOM_STD, MVS = MOM_MEAN | MOM_VAR | MOM_STD;
-    a.rescue = mom_rescue_slot();
+    a.rescue = c.worklist;
     if (a.rescue) {
         a.rescue_cap = (unsigned)(g.tiles_x * tiles_y);
-        if (mom_rescue_bytes(g.rows, g.cols) < 8 + 4 * (size_t)a.rescue_cap) a.rescue = nullptr;
+        if (c.worklist_bytes < 8 + 4 * (size_t)a.rescue_cap) a.rescue = nullptr;
         else {
             XRS_HIP(hipMemsetAsync(a.rescue, 0, 8, s));
-            a.exact = reinterpret_cast<unsigned *>(reinterpret_cast<char *>(a.rescue) + mom_exact_offset(g.rows, g.cols));
-            a.exact_cap = (unsigned)mom_exact_cap(g.rows, g.cols);
+            a.exact = c.exact;
+            a.exact_cap = c.exact_cap;
             XRS_HIP(hipMemsetAsync(a.exact, 0, 16, s));
         }
     }
@@ -849,10 +849,7 @@ int launch_mom(MomArgs &a, const double *kernel, hipStream_t s) {
     XRS_LAUNCH_CHECK();
     if (a.rescue) {
         // (the plane set at run time: one instantiation per shape; an empty list costs the launch, ~5 us)
-        int dev = 0, n_cu = 256;
-        hipDeviceProp_t prop;
-        static thread_local int cus = 0;
-        if (!cus) cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : n_cu;
+        const int cus = device_cu_count();
         hipLaunchKernelGGL((focal_mom_rescue_kernel<R, Shape, 0>), dim3((unsigned)(cus * 2)), dim3(256), 0, s, a);
         XRS_LAUNCH_CHECK();
         hipLaunchKernelGGL((focal_mom_exact_kernel<R, Shape>), dim3((unsigned)(cus * 2)), dim3(256), 0, s, a);
@@ -861,25 +858,27 @@ int launch_mom(MomArgs &a, const double *kernel, hipStream_t s) {
     return 0;
 }
 
+// the call's plane, geometry and sum / mean / var / std outputs; false: none of the four is wanted
+bool mom_args(MomArgs &a, const WindowCall &c) {
+    memset(&a, 0, sizeof(a));
+    fill_geom(a.g, c);
+    a.out_sum = c.out[XRS_STAT_SUM]; a.out_mean = c.out[XRS_STAT_MEAN]; a.out_var = c.out[XRS_STAT_VAR]; a.out_std = c.out[XRS_STAT_STD];
+    return a.out_sum || a.out_mean || a.out_var || a.out_std;
+}
+
 }  // namespace
 
 namespace xrs {
 
 #ifndef XRS_MOM_ANNULUS_R
 // 0 = launched, -1 = not this shape with a radius of 4..12 cells (caller takes another kernel), > 0 = error.
-int XRS_MOM_ENTRY(const float *in, float *out_sum, float *out_mean, float *out_var, float *out_std, long rows, long cols,
-                  long ld_in, long ld_out, const double *kernel, int krows, int kcols, int halo_top, int halo_bot,
-                  hipStream_t s, unsigned char *todo_dev) {
-    if (krows != kcols || !(krows & 1)) return -1;
-    if (!out_sum && !out_mean && !out_var && !out_std) return 0;
+int XRS_MOM_ENTRY(const WindowCall &c) {
+    if (c.mask.kind != ShapeKind<XRS_MOM_SHAPE>::kind) return -1;
     MomArgs a;
-    memset(&a, 0, sizeof(a));
-    a.g.in = in; a.g.rows = rows; a.g.cols = cols; a.g.ld_in = ld_in; a.g.ld_out = ld_out;
-    a.g.halo_top = halo_top; a.g.halo_bot = halo_bot;
-    a.out_sum = out_sum; a.out_mean = out_mean; a.out_var = out_var; a.out_std = out_std;
-    a.todo = todo_dev;
-    switch (krows / 2) {
-#define XRS_MOM_CASE(RR) case RR: return launch_mom<RR, XRS_MOM_SHAPE>(a, kernel, s);
+    if (!mom_args(a, c)) return 0;
+    if (std::is_same<XRS_MOM_SHAPE, BoxShape>::value) a.todo = c.box_todo;
+    switch (c.mask.R) {
+#define XRS_MOM_CASE(RR) case RR: return launch_mom<RR, XRS_MOM_SHAPE>(a, c);
         XRS_MOM_CASE(4) XRS_MOM_CASE(5) XRS_MOM_CASE(6) XRS_MOM_CASE(7) XRS_MOM_CASE(8) XRS_MOM_CASE(9) XRS_MOM_CASE(10) XRS_MOM_CASE(11)
         XRS_MOM_CASE(12)
 #undef XRS_MOM_CASE
@@ -890,26 +889,18 @@ int XRS_MOM_ENTRY(const float *in, float *out_sum, float *out_mean, float *out_v
 // annulus_kernel(1, 1, XRS_MOM_ANNULUS_R, RI), 1 <= RI < R: one instantiation per inner radius (one translation unit per
 // outer radius: the moments kernel is the slow one to compile).  0 = launched, -1 = not such an annulus, > 0 = error.
 template <int RI>
-int mom_annulus_pair(MomArgs &a, const double *kernel, int ri, hipStream_t s) {
+int mom_annulus_pair(MomArgs &a, const WindowCall &c) {
     if constexpr (RI >= XRS_MOM_ANNULUS_R) return -1;
     else {
-        if (ri == RI) return launch_mom<XRS_MOM_ANNULUS_R, AnnulusShape<RI>>(a, kernel, s);
-        return mom_annulus_pair<RI + 1>(a, kernel, ri, s);
+        if (c.mask.RI == RI) return launch_mom<XRS_MOM_ANNULUS_R, AnnulusShape<RI>>(a, c);
+        return mom_annulus_pair<RI + 1>(a, c);
     }
 }
-int XRS_MOM_ENTRY(const float *in, float *out_sum, float *out_mean, float *out_var, float *out_std, long rows, long cols,
-                  long ld_in, long ld_out, const double *kernel, int krows, int kcols, int halo_top, int halo_bot,
-                  hipStream_t s) {
-    if (krows != kcols || krows / 2 != XRS_MOM_ANNULUS_R || !(krows & 1)) return -1;
-    const int ri = annulus_inner_radius(kernel, krows);
-    if (ri < 1) return -1;
-    if (!out_sum && !out_mean && !out_var && !out_std) return 0;
+int XRS_MOM_ENTRY(const WindowCall &c) {
+    if (c.mask.kind != WindowMask::ANNULUS || c.mask.R != XRS_MOM_ANNULUS_R) return -1;
     MomArgs a;
-    memset(&a, 0, sizeof(a));
-    a.g.in = in; a.g.rows = rows; a.g.cols = cols; a.g.ld_in = ld_in; a.g.ld_out = ld_out;
-    a.g.halo_top = halo_top; a.g.halo_bot = halo_bot;
-    a.out_sum = out_sum; a.out_mean = out_mean; a.out_var = out_var; a.out_std = out_std;
-    return mom_annulus_pair<1>(a, kernel, ri, s);
+    if (!mom_args(a, c)) return 0;
+    return mom_annulus_pair<1>(a, c);
 }
 #endif
 

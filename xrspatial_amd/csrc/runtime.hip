@@ -70,6 +70,17 @@ int launch_cast(const void *src, float *dst, long n, hipStream_t s) {
 
 }  // namespace
 
+int xrs::device_cu_count() {
+    static thread_local int n_cu = 0;
+    if (!n_cu) {
+        int dev = 0;
+        hipDeviceProp_t prop;
+        n_cu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
+                   ? prop.multiProcessorCount : 256;
+    }
+    return n_cu;
+}
+
 extern "C" {
 
 int xrs_cast_f32(const void *src_dev, int src_dtype, float *dst_dev, int64_t n, void *stream) {

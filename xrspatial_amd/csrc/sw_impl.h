@@ -397,9 +397,8 @@ __global__ void __launch_bounds__(256, 2) focal_sw_kernel(const SwArgs a) {
 }
 
 template <int R, typename Shape, int NC>
-int launch_sw(SwArgs &a, const double *kernel, hipStream_t s) {
+int launch_sw(SwArgs &a, hipStream_t s) {
     using C = SwCfg<R, Shape, NC>;
-    if (!is_shape<R, Shape>(kernel)) return -1;
     WalkGeom &g = a.g;
     const long tiles_x = (g.cols + C::TW - 1) / C::TW;
     a.groups_x = (tiles_x + 3) / 4;
@@ -423,20 +422,17 @@ int launch_sw(SwArgs &a, const double *kernel, hipStream_t s) {
 namespace xrs {
 
 // 0 = launched, -1 = not this shape with a radius of 2 or 3 cells (caller takes another kernel), > 0 = error.
-// outs: XRS_STAT_* order, NULL = not wanted.
-int XRS_SW_ENTRY(const float *in, float *const *outs, long rows, long cols, long ld_in, long ld_out, const double *kernel,
-                 int krows, int kcols, int halo_top, int halo_bot, hipStream_t s) {
-    if (krows != kcols || !(krows & 1)) return -1;
+int XRS_SW_ENTRY(const WindowCall &c) {
+    if (c.mask.kind != ShapeKind<XRS_SW_SHAPE>::kind) return -1;
     SwArgs a;
     memset(&a, 0, sizeof(a));
-    a.g.in = in; a.g.rows = rows; a.g.cols = cols; a.g.ld_in = ld_in; a.g.ld_out = ld_out;
-    a.g.halo_top = halo_top; a.g.halo_bot = halo_bot;
+    fill_geom(a.g, c);
     bool any = false;
-    for (int i = 0; i < XRS_NUM_STATS; ++i) { a.out[i] = outs[i]; any |= outs[i] != nullptr; }
+    for (int i = 0; i < XRS_NUM_STATS; ++i) { a.out[i] = c.out[i]; any |= c.out[i] != nullptr; }
     if (!any) return 0;
-    switch (krows / 2) {
-        case 2: return launch_sw<2, XRS_SW_SHAPE, 4>(a, kernel, s);
-        case 3: return launch_sw<3, XRS_SW_SHAPE, 2>(a, kernel, s);
+    switch (c.mask.R) {
+        case 2: return launch_sw<2, XRS_SW_SHAPE, 4>(a, c.s);
+        case 3: return launch_sw<3, XRS_SW_SHAPE, 2>(a, c.s);
         default: return -1;
     }
 }

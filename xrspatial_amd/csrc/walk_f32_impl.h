@@ -24,8 +24,7 @@ int launch(WalkGeom &g, const WalkOuts &o, hipStream_t s) {
 }
 
 template <int R>
-int dispatch(WalkGeom &g, const WalkOuts &o, const double *kernel, bool with_moments, hipStream_t s) {
-    if (!is_shape<R, XRS_WALK_SHAPE>(kernel)) return -1;
+int dispatch(WalkGeom &g, const WalkOuts &o, bool with_moments, hipStream_t s) {
     const bool ws = o.sum, wm = o.max || o.min || o.range;
     if (with_moments) {
         if constexpr (R <= 3) return launch<R, true, true, true>(g, o, s);
@@ -41,31 +40,30 @@ int dispatch(WalkGeom &g, const WalkOuts &o, const double *kernel, bool with_mom
 namespace xrs {
 
 // 0 = launched, -1 = not the shape / a radius this file is instantiated for (caller walks the taps), > 0 = error.
-// out_mean / out_var / out_std non-null: all seven statistics in one kernel (radius 2 and 3 only).
-int XRS_WALK_ENTRY(const float *in, float *out_sum, float *out_max, float *out_min, float *out_range,
-                                float *out_mean, float *out_var, float *out_std, long rows, long cols, long ld_in,
-                                long ld_out, const double *kernel, int krows, int kcols, int halo_top, int halo_bot,
-                                hipStream_t s) {
-    if (krows != kcols || !(krows & 1)) return -1;
-    const bool moments = out_mean || out_var || out_std;
-    if (!out_sum && !out_max && !out_min && !out_range && !moments) return 0;
+// Mean / var / std among the outputs: all seven statistics in one kernel (radius 2 and 3 only).
+int XRS_WALK_ENTRY(const WindowCall &c) {
+    if (c.mask.kind != ShapeKind<XRS_WALK_SHAPE>::kind) return -1;
+    float *const *out = c.out;
+    const bool moments = out[XRS_STAT_MEAN] || out[XRS_STAT_VAR] || out[XRS_STAT_STD];
+    if (!out[XRS_STAT_SUM] && !out[XRS_STAT_MAX] && !out[XRS_STAT_MIN] && !out[XRS_STAT_RANGE] && !moments) return 0;
     WalkGeom g;
     memset(&g, 0, sizeof(g));
-    g.in = in; g.rows = rows; g.cols = cols; g.ld_in = ld_in; g.ld_out = ld_out;
-    g.halo_top = halo_top; g.halo_bot = halo_bot;
-    const WalkOuts o = {out_sum, out_max, out_min, out_range, out_mean, out_var, out_std};
-    switch (krows / 2) {
-        case 2: return dispatch<2>(g, o, kernel, moments, s);
-        case 3: return dispatch<3>(g, o, kernel, moments, s);
-        case 4: return dispatch<4>(g, o, kernel, moments, s);
-        case 5: return dispatch<5>(g, o, kernel, moments, s);
-        case 6: return dispatch<6>(g, o, kernel, moments, s);
-        case 7: return dispatch<7>(g, o, kernel, moments, s);
-        case 8: return dispatch<8>(g, o, kernel, moments, s);
-        case 9: return dispatch<9>(g, o, kernel, moments, s);
-        case 10: return dispatch<10>(g, o, kernel, moments, s);
-        case 11: return dispatch<11>(g, o, kernel, moments, s);
-        case 12: return dispatch<12>(g, o, kernel, moments, s);
+    fill_geom(g, c);
+    const WalkOuts o = {out[XRS_STAT_SUM], out[XRS_STAT_MAX], out[XRS_STAT_MIN], out[XRS_STAT_RANGE],
+                        out[XRS_STAT_MEAN], out[XRS_STAT_VAR], out[XRS_STAT_STD]};
+    hipStream_t s = c.s;
+    switch (c.mask.R) {
+        case 2: return dispatch<2>(g, o, moments, s);
+        case 3: return dispatch<3>(g, o, moments, s);
+        case 4: return dispatch<4>(g, o, moments, s);
+        case 5: return dispatch<5>(g, o, moments, s);
+        case 6: return dispatch<6>(g, o, moments, s);
+        case 7: return dispatch<7>(g, o, moments, s);
+        case 8: return dispatch<8>(g, o, moments, s);
+        case 9: return dispatch<9>(g, o, moments, s);
+        case 10: return dispatch<10>(g, o, moments, s);
+        case 11: return dispatch<11>(g, o, moments, s);
+        case 12: return dispatch<12>(g, o, moments, s);
         default: return -1;
     }
 }

@@ -855,21 +855,17 @@ __global__ void __launch_bounds__(256, 2) focal_wide_rescue_kernel(const WideArg
 
 template <int R, typename Shape, int MODE>
 int launch_wide_rescue(WideArgs &a, long tiles_y, hipStream_t s) {
-    static thread_local int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-                  ? prop.multiProcessorCount : 256;
-    }
+    const int cus = device_cu_count();
     hipLaunchKernelGGL((focal_wide_rescue_kernel<R, Shape, MODE>), dim3((unsigned)(cus * 2)), dim3(256), 0, s, a);
     XRS_LAUNCH_CHECK();
     return 0;
 }
 
 template <int R, typename Shape>
-int launch_wide(WideArgs &a, float *out_mean, float *out_sum, hipStream_t s) {
+int launch_wide(WideArgs &a, const WindowCall &c) {
     using C = WideCfg<R, Shape>;
+    float *const out_mean = c.out[XRS_STAT_MEAN], *const out_sum = c.out[XRS_STAT_SUM];
+    hipStream_t s = c.s;
     WalkGeom &g = a.g;
     g.tiles_x = (g.cols + C::TW - 1) / C::TW;
     static thread_local int wg_per_cu = 0;                     // (per instantiation: registers depend on the radius)
@@ -882,9 +878,9 @@ int launch_wide(WideArgs &a, float *out_mean, float *out_sum, hipStream_t s) {
     a.rim_first = 1;
     const long grid = RimFirst(a.groups_x, tiles_y, a.rim_first).grid();
     if (grid > 0x7fffffffL) return fail("focal mean: raster too large for one launch");
-    a.rescue = mom_rescue_slot();
+    a.rescue = c.worklist;
     a.rescue_cap = (unsigned)(g.tiles_x * tiles_y);
-    if (a.rescue && mom_rescue_bytes(g.rows, g.cols) < 8 + 4 * (size_t)a.rescue_cap) a.rescue = nullptr;
+    if (a.rescue && c.worklist_bytes < 8 + 4 * (size_t)a.rescue_cap) a.rescue = nullptr;
     if (out_mean) {
         a.out = out_mean;
         if (a.rescue) XRS_HIP(hipMemsetAsync(a.rescue, 0, 8, s));
@@ -907,9 +903,10 @@ int launch_wide(WideArgs &a, float *out_mean, float *out_sum, hipStream_t s) {
 }
 
 template <int R, typename Shape>
-int launch_wide_conv(WideArgs &a, float *out, const double *kernel, const double *weights_dev, hipStream_t s) {
+int launch_wide_conv(WideArgs &a, const WindowCall &c) {
     using C = WideCfg<R, Shape>;
-    if (!is_uniform_shape<R, Shape>(kernel, &a.wgt)) return -1;
+    hipStream_t s = c.s;
+    a.wgt = c.mask.weight;
     WalkGeom &g = a.g;
     g.tiles_x = (g.cols + C::TW - 1) / C::TW;
     static thread_local int wg_per_cu = 0;                     // (per instantiation: registers depend on the radius)
@@ -919,8 +916,8 @@ int launch_wide_conv(WideArgs &a, float *out, const double *kernel, const double
     g.n_tiles = g.tiles_x * tiles_y;
     a.groups_x = (g.tiles_x + 3) / 4;
     a.n_groups = a.groups_x * tiles_y;
-    a.weights = weights_dev;
-    a.out = out;
+    a.weights = c.weights_dev;
+    a.out = c.out_conv;
     a.rim_first = 1;
     const long grid = RimFirst(a.groups_x, tiles_y, a.rim_first).grid();
     if (grid > 0x7fffffffL) return fail("convolve_2d: raster too large for one launch");
@@ -929,87 +926,69 @@ int launch_wide_conv(WideArgs &a, float *out, const double *kernel, const double
     return 0;
 }
 
-#ifndef XRS_WIDE_ANNULUS_R
-int dispatch_wide_conv(WideArgs &a, float *out, const double *kernel, const double *weights_dev, int r, hipStream_t s) {
-    switch (r) {
-#define XRS_WIDE_CASE(RR) case RR: return launch_wide_conv<RR, XRS_WIDE_SHAPE>(a, out, kernel, weights_dev, s);
-        XRS_WIDE_CASE(3) XRS_WIDE_CASE(4) XRS_WIDE_CASE(5) XRS_WIDE_CASE(6) XRS_WIDE_CASE(7) XRS_WIDE_CASE(8)
-        XRS_WIDE_CASE(9) XRS_WIDE_CASE(10) XRS_WIDE_CASE(11)
-        XRS_WIDE_CASE(12)
-#undef XRS_WIDE_CASE
-        default: return -1;
-    }
-}
-
-int dispatch_wide(WideArgs &a, float *out_mean, float *out_sum, const double *kernel, int r, hipStream_t s) {
-    switch (r) {
-#define XRS_WIDE_CASE(RR) case RR: return is_shape<RR, XRS_WIDE_SHAPE>(kernel) ? launch_wide<RR, XRS_WIDE_SHAPE>(a, out_mean, out_sum, s) : -1;
-        XRS_WIDE_CASE(3) XRS_WIDE_CASE(4) XRS_WIDE_CASE(5) XRS_WIDE_CASE(6) XRS_WIDE_CASE(7) XRS_WIDE_CASE(8)
-        XRS_WIDE_CASE(9) XRS_WIDE_CASE(10) XRS_WIDE_CASE(11)
-        XRS_WIDE_CASE(12)
-#undef XRS_WIDE_CASE
-        default: return -1;
-    }
-}
-#else
-// annulus_kernel(1, 1, XRS_WIDE_ANNULUS_R, RI), 1 <= RI < R: one instantiation pair (mean, convolution) per inner radius, one
-// translation unit per outer radius (as kxk_mom_ann*.hip)
-template <int RI>
-int wide_annulus_pair(WideArgs &a, float *out_mean, float *out_conv, const double *kernel, const double *weights_dev, int ri, hipStream_t s) {
-    if constexpr (RI >= XRS_WIDE_ANNULUS_R) return -1;
-    else {
-        if (ri != RI) return wide_annulus_pair<RI + 1>(a, out_mean, out_conv, kernel, weights_dev, ri, s);
-        if (out_conv) return launch_wide_conv<XRS_WIDE_ANNULUS_R, AnnulusShape<RI>>(a, out_conv, kernel, weights_dev, s);
-        return is_shape<XRS_WIDE_ANNULUS_R, AnnulusShape<RI>>(kernel) ? launch_wide<XRS_WIDE_ANNULUS_R, AnnulusShape<RI>>(a, out_mean, nullptr, s) : -1;
-    }
-}
-#endif
-
 }  // namespace
 
 namespace xrs {
 
 #ifdef XRS_WIDE_ANNULUS_R
-// Exactly one of out_mean / out_conv.  0 = launched, -1 = not annulus_kernel(1, 1, XRS_WIDE_ANNULUS_R, RI) (for out_conv: times
-// one weight value), > 0 = error.  `weights_dev`: the kernel as float64 in device memory (convolution only).
-int XRS_WIDE_ENTRY(const float *in, float *out_mean, float *out_conv, long rows, long cols, long ld_in, long ld_out,
-                   const double *kernel, const double *weights_dev, int krows, int kcols, int halo_top, int halo_bot, hipStream_t s) {
-    if (krows != kcols || krows / 2 != XRS_WIDE_ANNULUS_R || !(krows & 1) || (!out_mean == !out_conv)) return -1;
-    // (the inner radius as the mask draws it: the first selected cell of the centre row, whatever its weight)
-    const int R = XRS_WIDE_ANNULUS_R;
-    int ri = -1;
-    while (ri + 1 <= R && kernel[R * krows + R + ri + 1] == 0.0) ++ri;
-    if (ri < 1 || ri >= R) return -1;
+// annulus_kernel(1, 1, XRS_WIDE_ANNULUS_R, RI), 1 <= RI < R: one instantiation pair (mean, convolution) per inner radius, one
+// translation unit per outer radius (as kxk_mom_ann*.hip)
+template <int RI>
+static int wide_annulus_pair(WideArgs &a, const WindowCall &c) {
+    if constexpr (RI >= XRS_WIDE_ANNULUS_R) return -1;
+    else {
+        if (c.mask.RI != RI) return wide_annulus_pair<RI + 1>(a, c);
+        if (c.out_conv) return launch_wide_conv<XRS_WIDE_ANNULUS_R, AnnulusShape<RI>>(a, c);
+        return launch_wide<XRS_WIDE_ANNULUS_R, AnnulusShape<RI>>(a, c);
+    }
+}
+// The mean (out[XRS_STAT_MEAN], no other statistic) or the convolution (out_conv), exactly one of the two.  0 = launched,
+// -1 = not annulus_kernel(1, 1, XRS_WIDE_ANNULUS_R, RI) (for out_conv: times one weight value), > 0 = error.
+// This walker has always drawn the hole from exact zeros (mask.hole_zero): a focal mask whose hole cells are merely "not 1"
+// is left to the moments walker.
+int XRS_WIDE_ENTRY(const WindowCall &c) {
+    float *const out_mean = c.out[XRS_STAT_MEAN];
+    if (c.mask.kind != WindowMask::ANNULUS || c.mask.R != XRS_WIDE_ANNULUS_R || !c.mask.hole_zero || (!out_mean == !c.out_conv)) return -1;
     WideArgs a;
     memset(&a, 0, sizeof(a));
-    a.g.in = in; a.g.rows = rows; a.g.cols = cols; a.g.ld_in = ld_in; a.g.ld_out = ld_out;
-    a.g.halo_top = halo_top; a.g.halo_bot = halo_bot;
-    return wide_annulus_pair<1>(a, out_mean, out_conv, kernel, weights_dev, ri, s);
+    fill_geom(a.g, c);
+    return wide_annulus_pair<1>(a, with_outputs(c, 1u << XRS_STAT_MEAN));
 }
 #else
-// 0 = launched, -1 = not this shape with a radius of 3..12 cells (caller takes another kernel), > 0 = error.
-// (mean and sum together: two launches)
-int XRS_WIDE_ENTRY(const float *in, float *out_mean, float *out_sum, long rows, long cols, long ld_in, long ld_out,
-                   const double *kernel, int krows, int kcols, int halo_top, int halo_bot, hipStream_t s) {
-    if (krows != kcols || !(krows & 1)) return -1;
-    if (!out_mean && !out_sum) return 0;
-    WideArgs a;
-    memset(&a, 0, sizeof(a));
-    a.g.in = in; a.g.rows = rows; a.g.cols = cols; a.g.ld_in = ld_in; a.g.ld_out = ld_out;
-    a.g.halo_top = halo_top; a.g.halo_bot = halo_bot;
-    return dispatch_wide(a, out_mean, out_sum, kernel, krows / 2, s);
-}
-
+// (the convolution entry stands first: kernels come out in the code object in the order their instantiations are asked for)
 // convolve_2d with one weight value on this shape (normalised circle_kernel / np.ones): 0 = launched, -1 = not that,
 // > 0 = error.  `weights_dev`: the kernel as float64 in device memory, for windows that hold a non-finite cell.
-int XRS_WIDE_CONV_ENTRY(const float *in, float *out, long rows, long cols, long ld_in, long ld_out, const double *kernel,
-                        const double *weights_dev, int krows, int kcols, int halo_top, int halo_bot, hipStream_t s) {
-    if (krows != kcols || !(krows & 1)) return -1;
+int XRS_WIDE_CONV_ENTRY(const WindowCall &c) {
+    if (c.mask.kind != ShapeKind<XRS_WIDE_SHAPE>::kind) return -1;
     WideArgs a;
     memset(&a, 0, sizeof(a));
-    a.g.in = in; a.g.rows = rows; a.g.cols = cols; a.g.ld_in = ld_in; a.g.ld_out = ld_out;
-    a.g.halo_top = halo_top; a.g.halo_bot = halo_bot;
-    return dispatch_wide_conv(a, out, kernel, weights_dev, krows / 2, s);
+    fill_geom(a.g, c);
+    switch (c.mask.R) {
+#define XRS_WIDE_CASE(RR) case RR: return launch_wide_conv<RR, XRS_WIDE_SHAPE>(a, c);
+        XRS_WIDE_CASE(3) XRS_WIDE_CASE(4) XRS_WIDE_CASE(5) XRS_WIDE_CASE(6) XRS_WIDE_CASE(7) XRS_WIDE_CASE(8)
+        XRS_WIDE_CASE(9) XRS_WIDE_CASE(10) XRS_WIDE_CASE(11)
+        XRS_WIDE_CASE(12)
+#undef XRS_WIDE_CASE
+        default: return -1;
+    }
+}
+
+// 0 = launched, -1 = not this shape with a radius of 3..12 cells (caller takes another kernel), > 0 = error.
+// (mean and sum together: two launches)
+int XRS_WIDE_ENTRY(const WindowCall &c) {
+    if (c.mask.kind != ShapeKind<XRS_WIDE_SHAPE>::kind) return -1;
+    if (!c.out[XRS_STAT_MEAN] && !c.out[XRS_STAT_SUM]) return 0;
+    WideArgs a;
+    memset(&a, 0, sizeof(a));
+    fill_geom(a.g, c);
+    switch (c.mask.R) {
+#define XRS_WIDE_CASE(RR) case RR: return launch_wide<RR, XRS_WIDE_SHAPE>(a, c);
+        XRS_WIDE_CASE(3) XRS_WIDE_CASE(4) XRS_WIDE_CASE(5) XRS_WIDE_CASE(6) XRS_WIDE_CASE(7) XRS_WIDE_CASE(8)
+        XRS_WIDE_CASE(9) XRS_WIDE_CASE(10) XRS_WIDE_CASE(11)
+        XRS_WIDE_CASE(12)
+#undef XRS_WIDE_CASE
+        default: return -1;
+    }
 }
 #endif
 

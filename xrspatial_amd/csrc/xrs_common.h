@@ -173,49 +173,10 @@ __device__ __forceinline__ void store_f4u(float *p, float x, float y, float z, f
     __builtin_nontemporal_store(q, reinterpret_cast<xrs_v4fu_st *>(p));
 }
 
-// kxk_runs.hip: prefix-sum focal mean for large run-structured masks.  0 = launched, -1 = mask not
-// suitable (caller uses the tap kernels), > 0 = error.
-int try_launch_focal_mean_runs(const float *in, float *out, long rows, long cols, long ld_in, long ld_out,
-                               const double *kernel, int krows, int kcols, int halo_top, int halo_bot,
-                               hipStream_t s);
-// same tiles, plus variance / standard deviation from a second prefix array (any output may be null)
-int try_launch_focal_meanvar_runs(const float *in, float *out_mean, float *out_var, float *out_std, long rows,
-                                  long cols, long ld_in, long ld_out, const double *kernel, int krows, int kcols,
-                                  int halo_top, int halo_bot, hipStream_t s);
+// runtime.hip: compute units of the current device (256 if the runtime will not say); asked once per thread
+int device_cu_count();
 
-// kxk_circle.hip: float32 sum / max / min / range for circular masks of radius 2..12 cells (column walker).
-// 0 = launched, -1 = not such a circle (caller walks the taps), > 0 = error.  Null outputs are skipped.
-// With any of out_mean / out_var / out_std non-null all seven statistics come from one kernel (radius 2, 3 only).
-int try_launch_focal_circle_f32(const float *in, float *out_sum, float *out_max, float *out_min, float *out_range,
-                                float *out_mean, float *out_var, float *out_std, long rows, long cols, long ld_in,
-                                long ld_out, const double *kernel, int krows, int kcols, int halo_top, int halo_bot,
-                                hipStream_t s);
-
-int try_launch_focal_box_f32(const float *in, float *out_sum, float *out_max, float *out_min, float *out_range,
-                             float *out_mean, float *out_var, float *out_std, long rows, long cols, long ld_in,
-                             long ld_out, const double *kernel, int krows, int kcols, int halo_top, int halo_bot,
-                             hipStream_t s);      // kxk_box.hip: the same for np.ones((k, k)) masks
-// kxk_circle64.hip / kxk_box64.hip: mean / var / std for the same shapes (float64 moments of shifted values, guarded).
-int try_launch_focal_box_f64(const float *in, float *out_mean, float *out_var, float *out_std, long rows, long cols,
-                             long ld_in, long ld_out, const double *kernel, int krows, int kcols, int halo_top,
-                             int halo_bot, hipStream_t s);
-int try_launch_focal_circle_f64(const float *in, float *out_mean, float *out_var, float *out_std, long rows, long cols,
-                                long ld_in, long ld_out, const double *kernel, int krows, int kcols, int halo_top,
-                                int halo_bot, hipStream_t s);
-
-// kxk_wide_circle.hip / kxk_wide_box.hip: focal mean / window sum, radius 3..12 cells, float32 on shifted values with a
-// guarded fall-back to the float64 walker (wide_impl.h).  0 = launched, -1 = not such a mask, > 0 = error.
-int try_launch_focal_wide_circle(const float *in, float *out_mean, float *out_sum, long rows, long cols, long ld_in,
-                                 long ld_out, const double *kernel, int krows, int kcols, int halo_top, int halo_bot,
-                                 hipStream_t s);
-int try_launch_focal_wide_box(const float *in, float *out_mean, float *out_sum, long rows, long cols, long ld_in,
-                              long ld_out, const double *kernel, int krows, int kcols, int halo_top, int halo_bot,
-                              hipStream_t s);
-// the same TUs: convolve_2d with one weight value on a circle / box of radius 3..12 cells (WIDE_CONV)
-int try_launch_conv_wide_circle(const float *in, float *out, long rows, long cols, long ld_in, long ld_out, const double *kernel,
-                                const double *weights_dev, int krows, int kcols, int halo_top, int halo_bot, hipStream_t s);
-int try_launch_conv_wide_box(const float *in, float *out, long rows, long cols, long ld_in, long ld_out, const double *kernel,
-                             const double *weights_dev, int krows, int kcols, int halo_top, int halo_bot, hipStream_t s);
+// (the window walkers' entry points: window_call.h)
 // kxk_big.hip: focal statistics / convolve_2d for windows beyond the tiled kernels' 63 x 63 (one thread per cell, window from
 // global memory, mask / weights from a device copy of the kernel in `work_dev`)
 int launch_window_any_size(bool conv, const float *in, float *const *outs, long rows, long cols, long ld_in, long ld_out,
@@ -223,76 +184,13 @@ int launch_window_any_size(bool conv, const float *in, float *const *outs, long 
                            hipStream_t s);
 // pass.hip: is this mask one of the compile-time masks of raster_pass_kernel (circle_kernel(1, 1, 2), np.ones((3, 3)))?
 bool pass_has_compile_time_mask(const double *kernel, int krows, int kcols);
-// kxk_ext_circle.hip / kxk_ext_box.hip (ext_impl.h): max / min / range, radius 4..12 cells, two input rows per step.
-int try_launch_focal_ext_circle(const float *in, float *out_max, float *out_min, float *out_range, long rows, long cols,
-                                long ld_in, long ld_out, const double *kernel, int krows, int kcols, int halo_top,
-                                int halo_bot, hipStream_t s);
-int try_launch_focal_ext_box(const float *in, float *out_max, float *out_min, float *out_range, long rows, long cols,
-                             long ld_in, long ld_out, const double *kernel, int krows, int kcols, int halo_top, int halo_bot,
-                             hipStream_t s);
-// kxk_mom_circle.hip / kxk_mom_box.hip (mom_impl.h): mean / var / std / sum, radius 4..12 cells, float32 sums about a
-// shift that trails the walk, guarded; exact float64 walker for the tiles that fail the guard.
-int try_launch_focal_mom_circle(const float *in, float *out_sum, float *out_mean, float *out_var, float *out_std, long rows,
-                                long cols, long ld_in, long ld_out, const double *kernel, int krows, int kcols, int halo_top,
-                                int halo_bot, hipStream_t s, unsigned char *todo_dev = nullptr);
-int try_launch_focal_mom_box(const float *in, float *out_sum, float *out_mean, float *out_var, float *out_std, long rows,
-                             long cols, long ld_in, long ld_out, const double *kernel, int krows, int kcols, int halo_top,
-                             int halo_bot, hipStream_t s, unsigned char *todo_dev = nullptr);
-// kxk_ext_ann_*.hip / kxk_mom_ann*.hip: the same two walkers for annulus_kernel(1, 1, R, RI), 4 <= R <= 12, 1 <= RI < R (one
-// instantiation per pair; the moments walkers one translation unit per outer radius).  0 = launched, -1 = not such an annulus.
-int try_launch_focal_ext_annulus_a(const float *in, float *out_max, float *out_min, float *out_range, long rows, long cols,
-                                   long ld_in, long ld_out, const double *kernel, int krows, int kcols, int halo_top, int halo_bot,
-                                   hipStream_t s);
-int try_launch_focal_ext_annulus_b(const float *in, float *out_max, float *out_min, float *out_range, long rows, long cols,
-                                   long ld_in, long ld_out, const double *kernel, int krows, int kcols, int halo_top, int halo_bot,
-                                   hipStream_t s);
-int try_launch_focal_ext_annulus_c(const float *in, float *out_max, float *out_min, float *out_range, long rows, long cols,
-                                   long ld_in, long ld_out, const double *kernel, int krows, int kcols, int halo_top, int halo_bot,
-                                   hipStream_t s);
-#define XRS_DECL_MOM_ANNULUS(RR)                                                                                              \
-    int try_launch_focal_mom_annulus##RR(const float *in, float *out_sum, float *out_mean, float *out_var, float *out_std,   \
-                                         long rows, long cols, long ld_in, long ld_out, const double *kernel, int krows,     \
-                                         int kcols, int halo_top, int halo_bot, hipStream_t s);
-XRS_DECL_MOM_ANNULUS(4) XRS_DECL_MOM_ANNULUS(5) XRS_DECL_MOM_ANNULUS(6) XRS_DECL_MOM_ANNULUS(7) XRS_DECL_MOM_ANNULUS(8)
-XRS_DECL_MOM_ANNULUS(9) XRS_DECL_MOM_ANNULUS(10) XRS_DECL_MOM_ANNULUS(11) XRS_DECL_MOM_ANNULUS(12)
-#undef XRS_DECL_MOM_ANNULUS
-// kxk_wide_ann4.hip .. kxk_wide_ann12.hip (wide_impl.h): the mean (out_mean) or the uniform-weight convolution (out_conv; exactly
-// one of the two) over annulus_kernel(1, 1, RR, RI).  0 = launched, -1 = not such a mask, > 0 = error.
-#define XRS_DECL_WIDE_ANNULUS(RR)                                                                                             \
-    int try_launch_wide_annulus##RR(const float *in, float *out_mean, float *out_conv, long rows, long cols, long ld_in,      \
-                                    long ld_out, const double *kernel, const double *weights_dev, int krows, int kcols,       \
-                                    int halo_top, int halo_bot, hipStream_t s);
-XRS_DECL_WIDE_ANNULUS(4) XRS_DECL_WIDE_ANNULUS(5) XRS_DECL_WIDE_ANNULUS(6) XRS_DECL_WIDE_ANNULUS(7) XRS_DECL_WIDE_ANNULUS(8)
-XRS_DECL_WIDE_ANNULUS(9) XRS_DECL_WIDE_ANNULUS(10) XRS_DECL_WIDE_ANNULUS(11) XRS_DECL_WIDE_ANNULUS(12)
-#undef XRS_DECL_WIDE_ANNULUS
-// kxk_sw_circle.hip / kxk_sw_box.hip (sw_impl.h): any of the seven statistics over circles / boxes of radius 2, 3 cells from one
-// pass of the strip walker (outs: XRS_STAT_* order, NULL = not wanted).  0 = launched, -1 = not such a mask, > 0 = error.
-int try_launch_focal_sw_circle(const float *in, float *const *outs, long rows, long cols, long ld_in, long ld_out,
-                               const double *kernel, int krows, int kcols, int halo_top, int halo_bot, hipStream_t s);
-int try_launch_focal_sw_box(const float *in, float *const *outs, long rows, long cols, long ld_in, long ld_out,
-                            const double *kernel, int krows, int kcols, int halo_top, int halo_bot, hipStream_t s);
 // boxsep.hip: the separable fast walk for np.ones((krows, kcols)) -- mean / var / std / sum sets WITH var or std (for the
 // mean or the sum alone it measured no faster than the wide row walker: 0.53 vs 0.55 ms at 25x25, 0.68 vs 0.47 at 11x11) --
 // in front of a fall-back kernel whose workgroup tiles (fb_group_cols x fb_tile_rows cells, fb_groups_x per tile row) it
 // marks in `todo` where it cannot stand for its results.  0 = launched, -1 = not for this walk (the caller runs its kernel
-// everywhere), > 0 = error.
+// everywhere), > 0 = error.  `todo`: WorkspaceLayout::todo_off (window_call.h).
 int launch_box_sep(const float *in, float *out_sum, float *out_mean, float *out_var, float *out_std,
                    long rows, long cols, long ld_in, long ld_out, int krows, int kcols, int halo_top, int halo_bot,
                    unsigned char *todo, long fb_groups_x, int fb_tile_rows, int fb_group_cols, hipStream_t s);
-// bytes of `todo` that is always enough for a rows x cols raster (host side of xrs_focal_workspace_bytes)
-inline size_t box_todo_bytes(long rows, long cols) { return (size_t)(cols / 512 + 2) * (size_t)(rows / 64 + 2); }
-// the moments kernels' work-list of wave tiles handed on to focal_mom_rescue_kernel (mom_impl.h): [0] count, [2..] tiles;
-// wave tiles are at least 64 columns x 16 rows
-// behind it (mom_exact_offset): the bands the rescue launch hands on to the float64 walker's own launch, 16 bytes each
-inline size_t mom_rescue_tiles(long rows, long cols) { return (size_t)(cols / 64 + 2) * (size_t)(rows / 16 + 2); }
-inline size_t mom_exact_offset(long rows, long cols) { return 256 + 4 * mom_rescue_tiles(rows, cols); }
-inline size_t mom_exact_cap(long rows, long cols) { return 2 * mom_rescue_tiles(rows, cols) + 8192; }
-inline size_t mom_rescue_bytes(long rows, long cols) { return mom_exact_offset(rows, cols) + 16 + 16 * mom_exact_cap(rows, cols); }
-// ... handed from xrs_focal_stats_f32 (kxk.hip, which owns the caller's workspace) to launch_mom (mom_impl.h, nine
-// translation units) without widening every entry point in between: set around the call, NULL otherwise
-inline unsigned *&mom_rescue_slot() {
-    static thread_local unsigned *p = nullptr;
-    return p;
-}
 
 }  // namespace xrs

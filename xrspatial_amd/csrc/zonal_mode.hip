@@ -726,13 +726,7 @@ int mode_impl(const int32_t *zidx, const VT *vals, long n, int nz, VT nodata, in
         }
     }
     {
-        static thread_local int cus = 0;
-        if (!cus) {
-            int dev = 0;
-            hipDeviceProp_t prop;
-            cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-                      ? prop.multiProcessorCount : 256;
-        }
+        const int cus = device_cu_count();
         long per_cu = 160 * 1024 / (SLOTS * (long)(sizeof(K) + 8) + 2304);
         if (per_cu > 8) per_cu = 8;                 // (2048 threads per CU)
         const long slots = ((long)cus * per_cu - 1) | 1;
