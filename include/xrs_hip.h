@@ -497,6 +497,28 @@ int xrs_viewshed_f32(const float *data_dev, int64_t rows, int64_t cols, int64_t 
 int xrs_viewshed_f64(const double *data_dev, int64_t rows, int64_t cols, int64_t view_row, int64_t view_col, double observer_elev,
                      double target_elev, double ew_res, double ns_res, void *work_dev, double *out_dev, void *stream);
 
+/* proximity / allocation / direction (xrspatial/proximity.py `_process`): for every cell of a rows x cols C-contiguous raster
+ * (`dtype`: XRS_DT_*) the exact nearest target, with the reference's float64 distance arithmetic rounded to float32, the
+ * sweep's order among equidistant targets and its max_distance cut.
+ *   targets    n_values == 0: cells that are non-zero and finite; else cells equal to one of the n_values 8-byte values at
+ *              values_dev, read as `values_kind` says: float64 (every cell compared as float64, NumPy's promotion), or int64 /
+ *              uint64 for integer rasters (compared as integers: values beyond 2^53 stay apart).
+ *   xs_dev / ys_dev: one float64 coordinate per column / row, finite and strictly monotonic (the caller checks).
+ *   gc_dev     GREAT_CIRCLE only (else may be null): np.radians(xs) (cols), np.radians(ys) (rows), np.cos(np.radians(ys))
+ *              (rows), one after the other.
+ *   metric     0 EUCLIDEAN, 1 GREAT_CIRCLE, 2 MANHATTAN (the reference's codes).
+ *   mode       0 proximity, 1 allocation, 2 direction: one float32 plane into out_dev; 3: all three planes, in that order.
+ *              | XRS_PROX_SCAN_ONLY: only the row scan (left / right nearest target columns and the list of non-empty rows
+ *              into work_dev); | XRS_PROX_SEARCH_ONLY: only the search, on a workspace that holds the same raster's scan.
+ *   work_dev   xrs_proximity_workspace_bytes(rows, cols) bytes, caller-owned.
+ * Three launches on the stream (scan, row list, search); cells without a target within max_distance are NaN. */
+enum { XRS_PROX_VALUES_F64 = 0, XRS_PROX_VALUES_I64 = 1, XRS_PROX_VALUES_U64 = 2 };
+enum { XRS_PROX_SCAN_ONLY = 16, XRS_PROX_SEARCH_ONLY = 32 };
+size_t xrs_proximity_workspace_bytes(int64_t rows, int64_t cols);
+int xrs_proximity(const void *data_dev, int dtype, int64_t rows, int64_t cols, const double *xs_dev, const double *ys_dev,
+                  const double *gc_dev, const void *values_dev, int values_kind, int n_values, double max_distance, int metric,
+                  int mode, void *work_dev, float *out_dev, void *stream);
+
 /* multispectral.true_color (xrspatial/multispectral.py:1334-1495).
  *   xrs_nan_minmax_f32: minmax_dev[0..1] = np.nanmin / np.nanmax of a float32 plane (NaN, NaN if it holds no number);
  *   xrs_true_color_u8:  rgba[i] = { stretch(red), stretch(green), stretch(blue), alpha } with

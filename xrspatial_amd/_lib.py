@@ -175,6 +175,9 @@ _PROTOTYPES = {
                          c_void_p],
     "xrs_viewshed_f64": [c_void_p, c_int64, c_int64, c_int64, c_int64, c_double, c_double, c_double, c_double, c_void_p, c_void_p,
                          c_void_p],
+    "xrs_proximity_workspace_bytes": [c_int64, c_int64],
+    "xrs_proximity": [c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_int,
+                      c_int, c_void_p, c_void_p, c_void_p],
     "xrs_comm_unique_id": [c_void_p],
     "xrs_comm_init_rank": [ctypes.POINTER(c_void_p), c_void_p, c_int, c_int],
     "xrs_comm_destroy": [c_void_p],
@@ -189,7 +192,8 @@ _PROTOTYPES = {
 _RESTYPES = {"xrs_kxk_workspace_bytes": c_size_t, "xrs_focal_workspace_bytes": c_size_t, "xrs_zonal_majority_workspace_bytes": c_size_t,
              "xrs_zonal_mode_workspace_bytes": c_size_t,
              "xrs_geodesic_workspace_bytes": c_size_t, "xrs_classify_workspace_bytes": c_size_t,
-             "xrs_regions_workspace_bytes": c_size_t, "xrs_viewshed_workspace_bytes": c_size_t}
+             "xrs_regions_workspace_bytes": c_size_t, "xrs_viewshed_workspace_bytes": c_size_t,
+             "xrs_proximity_workspace_bytes": c_size_t}
 
 EXPORTED = tuple(_PROTOTYPES)
 

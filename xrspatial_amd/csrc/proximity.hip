@@ -1,0 +1,368 @@
+// proximity / allocation / direction: the exact nearest target of every cell.
+//
+// Reference: xrspatial/proximity.py, a port of GDAL's four-pass line sweep in which a cell inherits the nearest target of three
+// neighbours -- serial along rows and from row to row, and a heuristic.  What is computed here is the minimum itself, with the
+// reference's arithmetic per candidate and the sweep's order among equidistant targets:
+//   distance   d32 = float32(_distance(xs[c], x2, ys[r], y2, metric)) in float64 on the coordinate values, uncontracted;
+//   winner     the smallest d32; among equal ones targets in rows r <= i come first, there the first in row-major order, among
+//              rows r > i the last in row-major order (one int64 key per candidate, smaller wins);
+//   kept       where float64(max_distance)^2 >= d32 * d32 (float32), else NaN.
+// One fact carries the search: along a fixed target row and strictly monotonic xs every metric is non-decreasing in |c - j|
+// (haversine while |dlon| <= 180 degrees), so a row's nearest target is its nearest one at or left of j, or its nearest one
+// right of j.  Longitudes in [-180, 180] may lie up to 360 degrees apart; beyond 180 degrees haversine falls again, so on a
+// raster that spans more than 180 degrees the row's first and last target are two more candidates.
+//   scan     one block per row: left[i][j] = largest c <= j holding a target, right[i][j] = smallest c > j, -1 for none.  A
+//            max-scan over (c + 1) left to right and one over (cols - c) right to left, each a wave scan (wave_reduce.h), the
+//            four wave totals through LDS and a carry from span to span of SPAN columns.  The row's flag says whether it holds
+//            a target at all; a one-block pass compacts the flags into the ascending list of non-empty rows.
+//   search   one thread per cell, a block on SPAN adjacent columns of one row, so the walk over rows is uniform: from the
+//            cell's place in the list outwards, above and below in turn, two candidates per row.  A side is finished for a
+//            lane once the row's lower bound (|dy|; R |dlat| (1 - 1e-12) for haversine) as float32 is strictly above the best
+//            d32 (rounding is monotonic, so no target of that row can tie) or its square is beyond max_distance^2.
+// Known limit: two targets of one row on one side of j share a d32 only beyond ~2^11.5 cells; the search sees the nearer one
+// (proximity is unaffected, allocation / direction may name the other of two float32-equidistant targets).
+// Contraction is off for the whole file: dx * dx + dy * dy must round as the reference's.
+#include "xrs_common.h"
+#include "wave_reduce.h"
+
+#include <cmath>
+#include <type_traits>
+
+#pragma clang fp contract(off)
+
+using namespace xrs;
+
+namespace {
+
+constexpr int SPAN = 256;                      // columns per scan step and per search block: four waves
+constexpr int EUCLIDEAN = 0, GREAT_CIRCLE = 1, MANHATTAN = 2;
+constexpr int MODE_PROXIMITY = 0, MODE_ALLOCATION = 1, MODE_DIRECTION = 2, MODE_ALL = 3;
+
+inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+struct Plan {
+    size_t left_off, right_off, flag_off, list_off, count_off, total;
+};
+Plan plan(size_t rows, size_t cols) {
+    Plan p;
+    p.left_off = 0;
+    p.right_off = up256(rows * cols * 4);
+    p.flag_off = p.right_off + up256(rows * cols * 4);
+    p.list_off = p.flag_off + up256(rows * 4);
+    p.count_off = p.list_off + up256(rows * 4);
+    p.total = p.count_off + 256;
+    return p;
+}
+
+// rule 1: non-zero and finite, or equal to one of `values` under NumPy's == (64-bit integers as integers)
+template <typename T>
+__device__ __forceinline__ bool is_target(T v, const void *__restrict__ values, int kind, int n) {
+    if (n == 0) {
+        if constexpr (std::is_floating_point<T>::value) return v != (T)0 && isfinite(v);
+        else return v != (T)0;
+    }
+    bool hit = false;
+    if constexpr (std::is_integral<T>::value) {
+        if (kind == XRS_PROX_VALUES_I64) {
+            const int64_t *q = static_cast<const int64_t *>(values);
+            for (int k = 0; k < n; ++k) {
+                if constexpr (std::is_unsigned<T>::value) hit |= q[k] >= 0 && (uint64_t)q[k] == (uint64_t)v;
+                else hit |= (int64_t)v == q[k];
+            }
+            return hit;
+        }
+        if (kind == XRS_PROX_VALUES_U64) {
+            const uint64_t *q = static_cast<const uint64_t *>(values);
+            for (int k = 0; k < n; ++k) {
+                if constexpr (std::is_unsigned<T>::value) hit |= (uint64_t)v == q[k];
+                else hit |= v >= 0 && (uint64_t)v == q[k];
+            }
+            return hit;
+        }
+    }
+    const double *q = static_cast<const double *>(values);
+    for (int k = 0; k < n; ++k) hit |= (double)v == q[k];
+    return hit;
+}
+
+// the four wave totals of step `it` (inclusive scans' last lanes): what lies before this wave, and everything
+__device__ __forceinline__ void fold_totals(const int (&tot)[2][4], int it, int wave, int carry, int &before, int &all) {
+    before = all = carry;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        const int t = tot[it & 1][w];
+        all = max(all, t);
+        if (w < wave) before = max(before, t);
+    }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(SPAN) proximity_scan_kernel(const T *__restrict__ data, long cols, const void *__restrict__ values,
+                                                              int kind, int n_values, int *__restrict__ left, int *__restrict__ right,
+                                                              int *__restrict__ flag) {
+    __shared__ int tot[2][4];                   // two steps' totals: one barrier per step
+    const long row = blockIdx.x;
+    const T *__restrict__ in = data + row * cols;
+    int *L = left + row * cols, *R = right + row * cols;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    int it = 0, carry = 0, before, all;
+    for (long base = 0; base < cols; base += SPAN, ++it) {              // left to right: the largest c + 1 so far
+        const long j = base + threadIdx.x;
+        const int v = (j < cols && is_target<T>(in[j], values, kind, n_values)) ? (int)j + 1 : 0;
+        const int inc = wave_scan_max_i32(v);
+        if (lane == 63) tot[it & 1][wave] = inc;
+        __syncthreads();
+        fold_totals(tot, it, wave, carry, before, all);
+        if (j < cols) L[j] = max(inc, before) - 1;
+        carry = all;
+    }
+    if (threadIdx.x == 0) flag[row] = carry > 0;
+    __syncthreads();                                                     // L is read back below by other lanes
+    carry = 0;
+    for (long hi = cols; hi > 0; hi -= SPAN, ++it) {                     // right to left: the largest cols - c so far
+        const long j = hi - 1 - threadIdx.x;
+        const int v = (j >= 0 && L[j] == (int)j) ? (int)(cols - j) : 0;
+        const int inc = wave_scan_max_i32(v);
+        if (lane == 63) tot[it & 1][wave] = inc;
+        __syncthreads();
+        fold_totals(tot, it, wave, carry, before, all);
+        int prev = __shfl_up(inc, 1);                                    // exclusive: c > j
+        if (lane == 0) prev = 0;
+        const int e = max(prev, before);
+        if (j >= 0) R[j] = e > 0 ? (int)(cols - e) : -1;
+        carry = all;
+    }
+}
+
+// the ascending list of rows whose flag is set, and its length
+__global__ void __launch_bounds__(SPAN) proximity_rows_kernel(const int *__restrict__ flag, long rows, int *__restrict__ list,
+                                                              int *__restrict__ count) {
+    __shared__ int tot[2][4];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    int it = 0, carry = 0;
+    for (long base = 0; base < rows; base += SPAN, ++it) {
+        const long r = base + threadIdx.x;
+        const int f = r < rows ? flag[r] : 0;
+        const int inc = wave_scan_i32(f);
+        if (lane == 63) tot[it & 1][wave] = inc;
+        __syncthreads();
+        int before = carry, all = carry;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const int t = tot[it & 1][w];
+            all += t;
+            if (w < wave) before += t;
+        }
+        if (f) list[before + inc - 1] = (int)r;
+        carry = all;
+    }
+    if (threadIdx.x == 0) *count = carry;
+}
+
+struct Search {
+    const void *data;
+    int dtype;
+    long rows, cols;
+    const double *xs, *ys, *lon, *lat, *coslat;  // lon / lat / coslat: np.radians(xs), np.radians(ys), np.cos(np.radians(ys))
+    const int *left, *right, *list, *count;
+    double max2;                                 // float64(max_distance)^2, +inf for an infinite one
+    int mode;
+    float *out;                                  // MODE_ALL: three planes
+};
+
+__device__ __forceinline__ float cell_as_f32(const void *data, int dtype, long idx) {
+    switch (dtype) {
+    case XRS_DT_I8: return (float)static_cast<const int8_t *>(data)[idx];
+    case XRS_DT_U8: return (float)static_cast<const uint8_t *>(data)[idx];
+    case XRS_DT_I16: return (float)static_cast<const int16_t *>(data)[idx];
+    case XRS_DT_U16: return (float)static_cast<const uint16_t *>(data)[idx];
+    case XRS_DT_I32: return (float)static_cast<const int32_t *>(data)[idx];
+    case XRS_DT_U32: return (float)static_cast<const uint32_t *>(data)[idx];
+    case XRS_DT_I64: return (float)static_cast<const int64_t *>(data)[idx];
+    case XRS_DT_U64: return (float)static_cast<const uint64_t *>(data)[idx];
+    case XRS_DT_F64: return (float)static_cast<const double *>(data)[idx];
+    default: return static_cast<const float *>(data)[idx];
+    }
+}
+
+// `_calc_direction(x2, xs[c], y2, ys[r])` of a target that is not the cell itself
+__device__ __forceinline__ float compass(double x, double y) {
+    double d = atan2(-y, x) * 57.29578;
+    if (d < 0) d = 90.0 - d;
+    else if (d > 90.0) d = 360.0 - d + 90.0;
+    else d = 90.0 - d;
+    return (float)d;
+}
+
+template <int METRIC>
+__global__ void __launch_bounds__(SPAN) proximity_search_kernel(const Search p) {
+    const long spans = (p.cols + SPAN - 1) / SPAN;
+    const long i = (long)blockIdx.x / spans;
+    const long j0 = ((long)blockIdx.x - i * spans) * SPAN + threadIdx.x;
+    const bool valid = j0 < p.cols;
+    const long j = valid ? j0 : p.cols - 1;                              // surplus lanes walk along and write nothing
+    const double x2 = p.xs[j], y2 = p.ys[i];
+    double lon2 = 0.0, lat2 = 0.0, cos2 = 0.0;
+    if (METRIC == GREAT_CIRCLE) { lon2 = p.lon[j]; lat2 = p.lat[i]; cos2 = p.coslat[i]; }
+    const long cells = p.rows * p.cols;
+    // longitudes more than 180 degrees apart: along a row haversine falls again beyond 180 degrees, so the row's first and
+    // last target are candidates too (the far end of the row may be the near one round the back of the sphere)
+    const bool wraps = METRIC == GREAT_CIRCLE && fabs(p.lon[p.cols - 1] - p.lon[0]) > 3.14159265358979323846;
+
+    // the last non-empty row at or above i
+    const int n = *p.count;
+    int lo = -1, hi = n;                                                 // list[lo] <= i < list[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (p.list[mid] <= i) lo = mid; else hi = mid;
+    }
+    int up = lo, dn = hi;
+
+    float best = INFINITY;
+    long best_key = 0x7fffffffffffffffL;
+    int best_r = -1, best_c = -1;
+    bool open_up = valid, open_dn = valid;
+
+    auto visit = [&](int r, bool &open, bool above) {
+        float bound;
+        if (METRIC == GREAT_CIRCLE) bound = (float)(6378137.0 * fabs(lat2 - p.lat[r]) * (1.0 - 1e-12));
+        else bound = (float)fabs(p.ys[r] - y2);
+        if (bound > best || (double)(bound * bound) > p.max2) { open = false; return; }
+        const long at = (long)r * p.cols;
+        int cand[4] = {p.left[at + j], p.right[at + j], -1, -1};
+        if (METRIC == GREAT_CIRCLE && wraps) {                           // the row's first and last target
+            cand[2] = p.left[at] == 0 ? 0 : p.right[at];
+            cand[3] = p.left[at + p.cols - 1];
+        }
+#pragma unroll
+        for (int k = 0; k < (METRIC == GREAT_CIRCLE ? 4 : 2); ++k) {
+            const int c = cand[k];
+            if (c < 0) continue;
+            double d;
+            if (METRIC == EUCLIDEAN) {
+                const double dx = p.xs[c] - x2, dy = p.ys[r] - y2;
+                d = sqrt(dx * dx + dy * dy);
+            } else if (METRIC == MANHATTAN) {
+                const double dx = p.xs[c] - x2, dy = p.ys[r] - y2;
+                d = fabs(dx) + fabs(dy);
+            } else {
+                const double dlon = lon2 - p.lon[c], dlat = lat2 - p.lat[r];
+                const double sa = sin(dlat / 2.0), so = sin(dlon / 2.0);
+                const double a = sa * sa + p.coslat[r] * cos2 * (so * so);
+                d = 12756274.0 * asin(sqrt(a));
+            }
+            const float d32 = (float)d;
+            const long key = above ? at + c : 2 * cells - (at + c);
+            if (d32 < best || (d32 == best && key < best_key)) { best = d32; best_key = key; best_r = r; best_c = c; }
+        }
+    };
+
+    while (true) {
+        const bool go_up = up >= 0 && __ballot(open_up) != 0, go_dn = dn < n && __ballot(open_dn) != 0;
+        if (!go_up && !go_dn) break;
+        if (go_up) {
+            if (open_up) visit(p.list[up], open_up, true);
+            --up;
+        }
+        if (go_dn) {
+            if (open_dn) visit(p.list[dn], open_dn, false);
+            ++dn;
+        }
+    }
+    if (!valid) return;
+
+    const float s = best * best;
+    const bool kept = best_r >= 0 && (p.max2 >= (double)s);
+    float prox = nan_f32(), alloc = nan_f32(), dir = nan_f32();
+    if (kept) {
+        prox = (float)sqrt((double)s);
+        if (p.mode == MODE_ALLOCATION || p.mode == MODE_ALL) alloc = cell_as_f32(p.data, p.dtype, (long)best_r * p.cols + best_c);
+        if (p.mode == MODE_DIRECTION || p.mode == MODE_ALL)
+            dir = (best_r == i && best_c == j) ? 0.0f : compass(p.xs[best_c] - x2, p.ys[best_r] - y2);
+    }
+    const long at = i * p.cols + j;
+    if (p.mode == MODE_ALL) {
+        p.out[at] = prox;
+        p.out[cells + at] = alloc;
+        p.out[2 * cells + at] = dir;
+    } else {
+        p.out[at] = p.mode == MODE_PROXIMITY ? prox : (p.mode == MODE_ALLOCATION ? alloc : dir);
+    }
+}
+
+template <typename T>
+void launch_scan(const void *data, long rows, long cols, const void *values, int kind, int n_values, int *left, int *right,
+                 int *flag, hipStream_t s) {
+    hipLaunchKernelGGL((proximity_scan_kernel<T>), dim3((unsigned)rows), dim3(SPAN), 0, s, static_cast<const T *>(data), cols, values,
+                       kind, n_values, left, right, flag);
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t xrs_proximity_workspace_bytes(int64_t rows, int64_t cols) {
+    return rows > 0 && cols > 0 ? plan((size_t)rows, (size_t)cols).total : 0;
+}
+
+int xrs_proximity(const void *data_dev, int dtype, int64_t rows, int64_t cols, const double *xs_dev, const double *ys_dev,
+                  const double *gc_dev, const void *values_dev, int values_kind, int n_values, double max_distance, int metric,
+                  int mode, void *work_dev, float *out_dev, void *stream) {
+    const int product = mode & 3;
+    const bool do_scan = !(mode & XRS_PROX_SEARCH_ONLY), do_search = !(mode & XRS_PROX_SCAN_ONLY);
+    if (rows < 0 || cols < 0) return fail("xrs_proximity: negative shape");
+    if (mode & ~(3 | XRS_PROX_SCAN_ONLY | XRS_PROX_SEARCH_ONLY) || !(do_scan || do_search))
+        return fail("xrs_proximity: unknown mode %d", mode);
+    if (metric != EUCLIDEAN && metric != GREAT_CIRCLE && metric != MANHATTAN) return fail("xrs_proximity: unknown metric %d", metric);
+    if (dtype < XRS_DT_I8 || dtype > XRS_DT_F32) return fail("xrs_proximity: unsupported dtype code %d", dtype);
+    if (n_values < 0) return fail("xrs_proximity: negative number of target values");
+    if (values_kind != XRS_PROX_VALUES_F64 && values_kind != XRS_PROX_VALUES_I64 && values_kind != XRS_PROX_VALUES_U64)
+        return fail("xrs_proximity: unknown kind of target values %d", values_kind);
+    if (values_kind != XRS_PROX_VALUES_F64 && (dtype == XRS_DT_F32 || dtype == XRS_DT_F64))
+        return fail("xrs_proximity: a float raster is compared with float64 target values");
+    if (rows == 0 || cols == 0) return 0;
+    if (rows >= (1L << 31) - SPAN || cols >= (1L << 31) - SPAN) return fail("xrs_proximity: raster too large (%lld x %lld)", (long long)rows, (long long)cols);
+    const long spans = (cols + SPAN - 1) / SPAN;
+    if (rows * spans >= (1L << 31)) return fail("xrs_proximity: raster too large for one call (%lld x %lld)", (long long)rows, (long long)cols);
+    if (!data_dev || !xs_dev || !ys_dev || !work_dev || (do_search && !out_dev) || (n_values > 0 && !values_dev))
+        return fail("xrs_proximity: null pointer");
+    if (metric == GREAT_CIRCLE && do_search && !gc_dev) return fail("xrs_proximity: GREAT_CIRCLE needs the coordinates in radians");
+    if (max_distance != max_distance) return fail("xrs_proximity: max_distance is NaN");
+
+    hipStream_t s = as_stream(stream);
+    const Plan pl = plan((size_t)rows, (size_t)cols);
+    char *base = static_cast<char *>(work_dev);
+    int *left = (int *)(base + pl.left_off), *right = (int *)(base + pl.right_off), *flag = (int *)(base + pl.flag_off);
+    int *list = (int *)(base + pl.list_off), *count = (int *)(base + pl.count_off);
+    if (do_scan) {
+#define XRS_PROX_SCAN(T) launch_scan<T>(data_dev, rows, cols, values_dev, values_kind, n_values, left, right, flag, s); break
+        switch (dtype) {
+        case XRS_DT_I8: XRS_PROX_SCAN(int8_t); case XRS_DT_U8: XRS_PROX_SCAN(uint8_t);
+        case XRS_DT_I16: XRS_PROX_SCAN(int16_t); case XRS_DT_U16: XRS_PROX_SCAN(uint16_t);
+        case XRS_DT_I32: XRS_PROX_SCAN(int32_t); case XRS_DT_U32: XRS_PROX_SCAN(uint32_t);
+        case XRS_DT_I64: XRS_PROX_SCAN(int64_t); case XRS_DT_U64: XRS_PROX_SCAN(uint64_t);
+        case XRS_DT_F64: XRS_PROX_SCAN(double); default: XRS_PROX_SCAN(float);
+        }
+#undef XRS_PROX_SCAN
+        XRS_LAUNCH_CHECK();
+        hipLaunchKernelGGL(proximity_rows_kernel, dim3(1), dim3(SPAN), 0, s, flag, (long)rows, list, count);
+        XRS_LAUNCH_CHECK();
+    }
+    if (do_search) {
+        Search p;
+        p.data = data_dev; p.dtype = dtype; p.rows = rows; p.cols = cols;
+        p.xs = xs_dev; p.ys = ys_dev;
+        p.lon = gc_dev; p.lat = gc_dev ? gc_dev + cols : nullptr; p.coslat = gc_dev ? gc_dev + cols + rows : nullptr;
+        p.left = left; p.right = right; p.list = list; p.count = count;
+        p.max2 = std::isinf(max_distance) ? INFINITY : max_distance * max_distance;
+        p.mode = product; p.out = out_dev;
+        const dim3 grid((unsigned)(rows * spans));
+        if (metric == EUCLIDEAN) hipLaunchKernelGGL((proximity_search_kernel<EUCLIDEAN>), grid, dim3(SPAN), 0, s, p);
+        else if (metric == MANHATTAN) hipLaunchKernelGGL((proximity_search_kernel<MANHATTAN>), grid, dim3(SPAN), 0, s, p);
+        else hipLaunchKernelGGL((proximity_search_kernel<GREAT_CIRCLE>), grid, dim3(SPAN), 0, s, p);
+        XRS_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
+}  // extern "C"

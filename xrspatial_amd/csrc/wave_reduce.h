@@ -98,4 +98,15 @@ __device__ __forceinline__ int wave_scan_i32(int v) {
     return v;
 }
 
+// inclusive max-scan of one NON-NEGATIVE int32 per lane (0 is the identity: a lane without a source reads 0)
+__device__ __forceinline__ int wave_scan_max_i32(int v) {
+    v = max(v, dpp_shr_i32<0x111>(v));
+    v = max(v, dpp_shr_i32<0x112>(v));
+    v = max(v, dpp_shr_i32<0x114>(v));
+    v = max(v, dpp_shr_i32<0x118>(v));
+    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false));
+    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false));
+    return v;
+}
+
 }  // namespace xrs
