@@ -339,6 +339,10 @@ int zonal_init(uint64_t *count_dev, double *sum_dev, double *sumsq_dev, VT *min_
     return 0;
 }
 
+constexpr size_t ZONAL_LDS_CAP = 144 * 1024;                     // of the CU's 160 KiB (one workgroup per CU beyond 64 KiB)
+template <typename VT> constexpr size_t zonal_lds_per_zone() { return 16 + 2 * sizeof(VT) + 4; }
+template <typename VT> constexpr int zonal_launch_zones() { return (int)(ZONAL_LDS_CAP / zonal_lds_per_zone<VT>()); }   // zones of one launch
+
 template <typename VT>
 int zonal_partials(const int32_t *zone_idx_dev, const VT *values_dev, int64_t n, int n_zones, VT nodata,
                    int has_nodata, double shift, uint64_t *count_dev, double *sum_dev, double *sumsq_dev, VT *min_dev,
@@ -356,12 +360,12 @@ int zonal_partials(const int32_t *zone_idx_dev, const VT *values_dev, int64_t n,
     a.count = reinterpret_cast<unsigned long long *>(count_dev);
     a.sum = sum_dev; a.sumsq = sumsq_dev; a.mn = min_dev; a.mx = max_dev;
     a.present = present_dev; a.overflow = overflow_dev;
-    const size_t lds_cap = 144 * 1024;                           // of the CU's 160 KiB (one workgroup per CU beyond 64 KiB)
-    const size_t per_zone = 16 + 2 * sizeof(VT) + 4;
+    const size_t lds_cap = ZONAL_LDS_CAP;
+    const size_t per_zone = zonal_lds_per_zone<VT>();
     // More zones than LDS holds: several launches, each accumulating one window of zone indices in LDS (cells of other
     // windows are skipped).  A 5000-zone window streams the raster in ~1.5 ms; device atomics on the full table took
     // 21 ms for the same raster.
-    const int window = (int)(lds_cap / per_zone);
+    const int window = zonal_launch_zones<VT>();
     if (overflow_dev && n_zones > window) return fail("xrs_zonal_partials_window: at most %d ids per window", window);
     const bool vec = aligned16(zone_idx_dev) && aligned16(values_dev);
     hipStream_t s = as_stream(stream);
@@ -464,6 +468,8 @@ int zonal_window(const int32_t *zones_dev, int32_t zone_base, int window, const 
                  unsigned char *present_dev, int32_t *overflow_dev, void *stream) {
     if (window <= 0) return fail("xrs_zonal_partials_window: empty window");
     if (!present_dev || !overflow_dev) return fail("xrs_zonal_partials_window: null pointer");
+    // (refused before the tables are touched: zonal_partials' own test comes after the initialisation below)
+    if (window > zonal_launch_zones<VT>()) return fail("xrs_zonal_partials_window: at most %d ids per window", zonal_launch_zones<VT>());
     if (int rc = zonal_init<VT>(count_dev, sum_dev, sumsq_dev, min_dev, max_dev, window, stream)) return rc;
     XRS_HIP(hipMemsetAsync(present_dev, 0, (size_t)window, as_stream(stream)));
     XRS_HIP(hipMemsetAsync(overflow_dev, 0, sizeof(int32_t), as_stream(stream)));
