@@ -519,6 +519,33 @@ int xrs_proximity(const void *data_dev, int dtype, int64_t rows, int64_t cols, c
                   const double *gc_dev, const void *values_dev, int values_kind, int n_values, double max_distance, int metric,
                   int mode, void *work_dev, float *out_dev, void *stream);
 
+/* local (xrspatial/local.py): one result per cell from the same cell of n_planes equally sized, C-contiguous planes, each read
+ * in its own dtype (XRS_DT_* except XRS_DT_U64).  `planes` and `dtypes` are HOST arrays of n_planes (1 .. XRS_LOCAL_MAX_PLANES)
+ * device pointers and codes; they travel in the kernel's argument block.  The rule is DESIGN.md §6f.  The working type is
+ * int64 when every plane (and `ref_dev`, where the function reads one) is an integer and the function is not mean, median or
+ * std, else float64.
+ *   xrs_local_cells   op: XRS_LOCAL_*; ref_dev / ref_dtype: the plane of ref_var for the frequencies, rank and popularity (an
+ *                     integer plane for the last two), ignored otherwise.  out_dev: n 8-byte results, int64 if out_is_i64
+ *                     (integer working type only; not rank and popularity, which can give NaN), else float64.
+ *   xrs_local_combine 1-based ids of the cells' tuples in order of first occurrence, NaN where a plane is NaN, as float64 into
+ *                     out_dev; n < 2^31.  First call, first_cells_dev == NULL: computes out_dev and *n_classes and leaves the
+ *                     classes' first cells in work_dev (xrs_local_combine_workspace_bytes(n, n_planes) bytes, caller-owned;
+ *                     the call synchronises the stream).  Second call, same workspace, first_cells_dev with room for
+ *                     first_capacity >= *n_classes entries: copies them there, in id order.
+ *   xrs_local_gather  out_dev[t * n_planes + j] = plane j at cell cells_dev[t] as 8 bytes: int64 for an integer plane, float64
+ *                     for a floating one (the values of combine's key). */
+enum { XRS_LOCAL_MAX_PLANES = 64 };
+enum { XRS_LOCAL_MAX = 0, XRS_LOCAL_MIN = 1, XRS_LOCAL_SUM = 2, XRS_LOCAL_MEAN = 3, XRS_LOCAL_STD = 4, XRS_LOCAL_MEDIAN = 5,
+       XRS_LOCAL_LESSER = 6, XRS_LOCAL_EQUAL = 7, XRS_LOCAL_GREATER = 8, XRS_LOCAL_LOWEST = 9, XRS_LOCAL_HIGHEST = 10,
+       XRS_LOCAL_RANK = 11, XRS_LOCAL_POPULARITY = 12 };
+int xrs_local_cells(int op, const void *const *planes, const int *dtypes, int n_planes, const void *ref_dev, int ref_dtype,
+                    int64_t n, void *out_dev, int out_is_i64, void *stream);
+size_t xrs_local_combine_workspace_bytes(int64_t n, int n_planes);
+int xrs_local_combine(const void *const *planes, const int *dtypes, int n_planes, int64_t n, void *work_dev, size_t work_bytes,
+                      double *out_dev, unsigned *first_cells_dev, int64_t first_capacity, int64_t *n_classes, void *stream);
+int xrs_local_gather(const void *const *planes, const int *dtypes, int n_planes, int64_t n, const unsigned *cells_dev,
+                     int64_t n_cells, void *out_dev, void *stream);
+
 /* multispectral.true_color (xrspatial/multispectral.py:1334-1495).
  *   xrs_nan_minmax_f32: minmax_dev[0..1] = np.nanmin / np.nanmax of a float32 plane (NaN, NaN if it holds no number);
  *   xrs_true_color_u8:  rgba[i] = { stretch(red), stretch(green), stretch(blue), alpha } with

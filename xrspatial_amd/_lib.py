@@ -178,6 +178,12 @@ _PROTOTYPES = {
     "xrs_proximity_workspace_bytes": [c_int64, c_int64],
     "xrs_proximity": [c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_int,
                       c_int, c_void_p, c_void_p, c_void_p],
+    "xrs_local_cells": [c_int, ctypes.POINTER(c_void_p), ctypes.POINTER(c_int), c_int, c_void_p, c_int, c_int64, c_void_p, c_int,
+                        c_void_p],
+    "xrs_local_combine_workspace_bytes": [c_int64, c_int],
+    "xrs_local_combine": [ctypes.POINTER(c_void_p), ctypes.POINTER(c_int), c_int, c_int64, c_void_p, c_size_t, c_void_p, c_void_p,
+                          c_int64, ctypes.POINTER(c_int64), c_void_p],
+    "xrs_local_gather": [ctypes.POINTER(c_void_p), ctypes.POINTER(c_int), c_int, c_int64, c_void_p, c_int64, c_void_p, c_void_p],
     "xrs_comm_unique_id": [c_void_p],
     "xrs_comm_init_rank": [ctypes.POINTER(c_void_p), c_void_p, c_int, c_int],
     "xrs_comm_destroy": [c_void_p],
@@ -193,7 +199,7 @@ _RESTYPES = {"xrs_kxk_workspace_bytes": c_size_t, "xrs_focal_workspace_bytes": c
              "xrs_zonal_mode_workspace_bytes": c_size_t,
              "xrs_geodesic_workspace_bytes": c_size_t, "xrs_classify_workspace_bytes": c_size_t,
              "xrs_regions_workspace_bytes": c_size_t, "xrs_viewshed_workspace_bytes": c_size_t,
-             "xrs_proximity_workspace_bytes": c_size_t}
+             "xrs_proximity_workspace_bytes": c_size_t, "xrs_local_combine_workspace_bytes": c_size_t}
 
 EXPORTED = tuple(_PROTOTYPES)
 
