@@ -519,6 +519,35 @@ int xrs_proximity(const void *data_dev, int dtype, int64_t rows, int64_t cols, c
                   const double *gc_dev, const void *values_dev, int values_kind, int n_values, double max_distance, int metric,
                   int mode, void *work_dev, float *out_dev, void *stream);
 
+/* a_star_search (xrspatial/pathfinding.py:145-230 `_a_star_search`, :86-106 `_find_nearest_pixel`, :233-382 `a_star_search`): the
+ * shortest 4- or 8-connected path from (start_row, start_col) to (goal_row, goal_col) over the crossable cells of a rows x cols
+ * C-contiguous raster (`dtype`: XRS_DT_*; at most XRS_ASTAR_MAX_CELLS cells), as the exact shortest-distance field from the goal
+ * and one walk along it from the start.  Steps cost 1.0 along rows and columns and sqrt(2) diagonally.
+ *   crossable  not NaN and equal to none of the n_barriers 8-byte values at barriers_dev, read as `barriers_kind` says
+ *              (XRS_PROX_VALUES_*, as xrs_proximity reads its target values).
+ *   snap_flags XRS_ASTAR_SNAP_START / XRS_ASTAR_SNAP_GOAL: a start / goal that is not crossable moves to the crossable cell at
+ *              the smallest squared pixel distance, the first in row-major order among equals, strictly nearer than the raster's
+ *              diagonal; to (-1, -1) when there is none.  XRS_ASTAR_NO_WALK: the field only, out_dev stays NaN.  Bits 8 .. 15:
+ *              relaxation passes per host round trip, 1 .. 64 (0: the default).
+ *   work_dev   xrs_astar_workspace_bytes(rows, cols) bytes, caller-owned (0 for an empty or too large raster).
+ *   out_dev    float64: 0.0 at the start, the running sum of the step costs in walk order at every further cell of the path,
+ *              NaN everywhere else; all NaN when there is no path.
+ *   status_host HOST array of 8 words: start row, start col, goal row, goal col after snapping (-1, -1: none); flags; a and b,
+ *              the path's numbers of straight and diagonal steps (-1 without a path); relaxation passes run.  Flags:
+ *              XRS_ASTAR_START_CROSSABLE / XRS_ASTAR_GOAL_CROSSABLE tell of the cell the reference's warning looks at, which
+ *              for (-1, -1) is the raster's last cell; XRS_ASTAR_PATH_FOUND.
+ * The call waits for the stream (once per group of passes).  At most rows * cols + 2 passes; beyond that it fails.
+ * xrs_astar_tile_visits: how many tiles (64 x 32 cells; each loads 66 x 34 words of the field) the passes of the last xrs_astar
+ * call on this workspace worked on, summed over the passes -- what tools/pathfinding_bench.py turns into bytes per pass. */
+enum { XRS_ASTAR_SNAP_START = 1, XRS_ASTAR_SNAP_GOAL = 2, XRS_ASTAR_NO_WALK = 4, XRS_ASTAR_GROUP_SHIFT = 8 };
+enum { XRS_ASTAR_START_CROSSABLE = 1, XRS_ASTAR_GOAL_CROSSABLE = 2, XRS_ASTAR_PATH_FOUND = 4 };
+enum { XRS_ASTAR_MAX_CELLS = 1 << 30 };
+size_t xrs_astar_workspace_bytes(int64_t rows, int64_t cols);
+int xrs_astar(const void *data_dev, int dtype, int64_t rows, int64_t cols, int64_t start_row, int64_t start_col, int64_t goal_row,
+              int64_t goal_col, const void *barriers_dev, int barriers_kind, int n_barriers, int connectivity, int snap_flags,
+              void *work_dev, double *out_dev, int64_t *status_host, void *stream);
+int xrs_astar_tile_visits(const void *work_dev, int64_t rows, int64_t cols, int64_t *visits_host, void *stream);
+
 /* local (xrspatial/local.py): one result per cell from the same cell of n_planes equally sized, C-contiguous planes, each read
  * in its own dtype (XRS_DT_* except XRS_DT_U64).  `planes` and `dtypes` are HOST arrays of n_planes (1 .. XRS_LOCAL_MAX_PLANES)
  * device pointers and codes; they travel in the kernel's argument block.  The rule is DESIGN.md §6f.  The working type is

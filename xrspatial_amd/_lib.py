@@ -178,6 +178,10 @@ _PROTOTYPES = {
     "xrs_proximity_workspace_bytes": [c_int64, c_int64],
     "xrs_proximity": [c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_int,
                       c_int, c_void_p, c_void_p, c_void_p],
+    "xrs_astar_workspace_bytes": [c_int64, c_int64],
+    "xrs_astar": [c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int, c_int, c_int, c_int,
+                  c_void_p, c_void_p, ctypes.POINTER(c_int64), c_void_p],
+    "xrs_astar_tile_visits": [c_void_p, c_int64, c_int64, ctypes.POINTER(c_int64), c_void_p],
     "xrs_local_cells": [c_int, ctypes.POINTER(c_void_p), ctypes.POINTER(c_int), c_int, c_void_p, c_int, c_int64, c_void_p, c_int,
                         c_void_p],
     "xrs_local_combine_workspace_bytes": [c_int64, c_int],
@@ -199,7 +203,8 @@ _RESTYPES = {"xrs_kxk_workspace_bytes": c_size_t, "xrs_focal_workspace_bytes": c
              "xrs_zonal_mode_workspace_bytes": c_size_t,
              "xrs_geodesic_workspace_bytes": c_size_t, "xrs_classify_workspace_bytes": c_size_t,
              "xrs_regions_workspace_bytes": c_size_t, "xrs_viewshed_workspace_bytes": c_size_t,
-             "xrs_proximity_workspace_bytes": c_size_t, "xrs_local_combine_workspace_bytes": c_size_t}
+             "xrs_proximity_workspace_bytes": c_size_t, "xrs_local_combine_workspace_bytes": c_size_t,
+             "xrs_astar_workspace_bytes": c_size_t}
 
 EXPORTED = tuple(_PROTOTYPES)
 

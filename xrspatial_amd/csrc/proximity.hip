@@ -23,6 +23,7 @@
 // (proximity is unaffected, allocation / direction may name the other of two float32-equidistant targets).
 // Contraction is off for the whole file: dx * dx + dy * dy must round as the reference's.
 #include "xrs_common.h"
+#include "value_match.h"
 #include "wave_reduce.h"
 
 #include <cmath>
@@ -61,28 +62,7 @@ __device__ __forceinline__ bool is_target(T v, const void *__restrict__ values, 
         if constexpr (std::is_floating_point<T>::value) return v != (T)0 && isfinite(v);
         else return v != (T)0;
     }
-    bool hit = false;
-    if constexpr (std::is_integral<T>::value) {
-        if (kind == XRS_PROX_VALUES_I64) {
-            const int64_t *q = static_cast<const int64_t *>(values);
-            for (int k = 0; k < n; ++k) {
-                if constexpr (std::is_unsigned<T>::value) hit |= q[k] >= 0 && (uint64_t)q[k] == (uint64_t)v;
-                else hit |= (int64_t)v == q[k];
-            }
-            return hit;
-        }
-        if (kind == XRS_PROX_VALUES_U64) {
-            const uint64_t *q = static_cast<const uint64_t *>(values);
-            for (int k = 0; k < n; ++k) {
-                if constexpr (std::is_unsigned<T>::value) hit |= (uint64_t)v == q[k];
-                else hit |= v >= 0 && (uint64_t)v == q[k];
-            }
-            return hit;
-        }
-    }
-    const double *q = static_cast<const double *>(values);
-    for (int k = 0; k < n; ++k) hit |= (double)v == q[k];
-    return hit;
+    return matches_any<T>(v, values, kind, n);
 }
 
 // the four wave totals of step `it` (inclusive scans' last lanes): what lies before this wave, and everything

@@ -24,6 +24,12 @@ __device__ __forceinline__ double wr_dpp(double v) {
     return __hiloint2double((int)hi, (int)lo);
 }
 
+template <int CTRL, bool ZERO>
+__device__ __forceinline__ long long wr_dpp(long long v) {
+    const unsigned lo = wr_dpp<CTRL, ZERO>((unsigned)v), hi = wr_dpp<CTRL, ZERO>((unsigned)((unsigned long long)v >> 32));
+    return (long long)(((unsigned long long)hi << 32) | lo);
+}
+
 struct WrSum { template <typename T> __device__ __forceinline__ static T f(T a, T b) { return a + b; } static constexpr bool zero = true; };
 struct WrMin { template <typename T> __device__ __forceinline__ static T f(T a, T b) { return b < a ? b : a; } static constexpr bool zero = false; };
 struct WrMax { template <typename T> __device__ __forceinline__ static T f(T a, T b) { return a < b ? b : a; } static constexpr bool zero = false; };
@@ -43,6 +49,11 @@ __device__ __forceinline__ int wr_lane(int v, int l) { return __builtin_amdgcn_r
 __device__ __forceinline__ float wr_lane(float v, int l) { return __uint_as_float(wr_lane(__float_as_uint(v), l)); }
 __device__ __forceinline__ double wr_lane(double v, int l) {
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
+}
+
+__device__ __forceinline__ long long wr_lane(long long v, int l) {
+    const unsigned lo = wr_lane((unsigned)v, l), hi = wr_lane((unsigned)((unsigned long long)v >> 32), l);
+    return (long long)(((unsigned long long)hi << 32) | lo);
 }
 
 // all 64 lanes; the result is wave-uniform
