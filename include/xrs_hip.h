@@ -548,6 +548,36 @@ int xrs_astar(const void *data_dev, int dtype, int64_t rows, int64_t cols, int64
               void *work_dev, double *out_dev, int64_t *status_host, void *stream);
 int xrs_astar_tile_visits(const void *work_dev, int64_t rows, int64_t cols, int64_t *visits_host, void *stream);
 
+/* polygonize (xrspatial/experimental/polygonize.py:247-345 `_calculate_regions`, :105-207 `_follow`, :406-448 `_scan`): the
+ * polygon rings of the connected regions of a rows x cols C-contiguous raster (`dtype`: XRS_DT_*; at most 2^32 - 1 cells), 4- or
+ * 8-connected, in the reference's polygon order, ring order, start vertex and vertex sequence (the closed form: DESIGN.md §6h).
+ * Three calls on one stream, same raster and shape; the first two wait for the stream (once, and once per group of rounds):
+ *   xrs_polygonize_census   mask_dev: NULL or a plane of `mask_dtype` (XRS_DT_*; bool as XRS_DT_U8), a cell counts where it is
+ *              != 0.  work_dev: xrs_polygonize_workspace_bytes(rows, cols) bytes, caller-owned; its first rows * cols uint32
+ *              words are the region plane afterwards (0 = masked, else 1 + the number of regions whose first cell comes earlier).
+ *              *n_regions, *n_states (host): the number of regions and of boundary states (cell, direction E / N / W / S, with
+ *              the cell on the right-hand side outside the region).  No further call is needed when *n_states is 0.
+ *   xrs_polygonize_rings    rings_dev: xrs_polygonize_rings_workspace_bytes(n_states) bytes, caller-owned (0 when n_states is 0 or
+ *              above XRS_POLYGONIZE_MAX_STATES).  *n_rings, *n_points (host): the number of rings, and of points with every
+ *              ring's closing point.  rounds (host, 2 words or NULL): the pointer-doubling rounds run to find every ring's start
+ *              and to rank its states; each is bounded by 32, beyond which the call fails.
+ *   xrs_polygonize_scatter  transform_host: NULL or 6 doubles, x = t0 * i + t1 * j + t2, y = t3 * i + t4 * j + t5 with separately
+ *              rounded products and sums.  points_dev: float64 [n_points][2]; ring_offsets_dev: int64 [n_rings + 1], ring k
+ *              owns points ring_offsets[k] .. ring_offsets[k + 1]; polygon_offsets_dev: int64 [n_regions + 1], polygon p (region
+ *              p + 1) owns rings polygon_offsets[p] .. polygon_offsets[p + 1], the exterior first, then the holes by start cell;
+ *              column_dev: [n_regions] values of the raster's dtype, each region's first cell.  Does not wait for the stream. */
+#define XRS_POLYGONIZE_MAX_STATES 2147483647ull
+size_t xrs_polygonize_workspace_bytes(int64_t rows, int64_t cols);
+size_t xrs_polygonize_rings_workspace_bytes(uint64_t n_states);
+int xrs_polygonize_census(const void *data_dev, int dtype, const void *mask_dev, int mask_dtype, int64_t rows, int64_t cols,
+                          int connectivity, void *work_dev, uint64_t *n_regions, uint64_t *n_states, void *stream);
+int xrs_polygonize_rings(int64_t rows, int64_t cols, const void *work_dev, void *rings_dev, uint64_t n_states,
+                         uint64_t n_regions, uint64_t *n_rings, uint64_t *n_points, int *rounds, void *stream);
+int xrs_polygonize_scatter(const void *data_dev, int dtype, int64_t rows, int64_t cols, const void *work_dev,
+                           const void *rings_dev, uint64_t n_states, uint64_t n_regions, uint64_t n_rings,
+                           const double *transform_host, void *points_dev, void *ring_offsets_dev, void *polygon_offsets_dev,
+                           void *column_dev, void *stream);
+
 /* local (xrspatial/local.py): one result per cell from the same cell of n_planes equally sized, C-contiguous planes, each read
  * in its own dtype (XRS_DT_* except XRS_DT_U64).  `planes` and `dtypes` are HOST arrays of n_planes (1 .. XRS_LOCAL_MAX_PLANES)
  * device pointers and codes; they travel in the kernel's argument block.  The rule is DESIGN.md §6f.  The working type is

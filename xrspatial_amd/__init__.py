@@ -4,7 +4,8 @@ Drop-in for the `xrspatial.*` functions on that path (same names, signatures, Da
 in/out): slope, aspect, hillshade, curvature, focal.mean / apply / focal_stats,
 convolution.convolve_2d / convolution_2d, multispectral ndvi / evi / savi (+ nbr, nbr2, ndmi),
 zonal.stats, zonal.regions, classify (binary, reclassify, equal_interval, quantile, percentiles, box_plot, std_mean,
-head_tail_breaks, maximum_breaks), perlin, generate_terrain, viewshed, proximity / allocation / direction, a_star_search, local (cell_stats, combine, the frequencies, positions, rank, popularity).  Python host code calling hand-written HIP kernels through the C ABI of
+head_tail_breaks, maximum_breaks), perlin, generate_terrain, viewshed, proximity / allocation / direction, a_star_search, local (cell_stats, combine, the frequencies, positions, rank, popularity),
+experimental.polygonize.  Python host code calling hand-written HIP kernels through the C ABI of
 libxrs_hip.so (include/xrs_hip.h); no PyTorch, CuPy, Numba or Triton involved.
 
     import xrspatial_amd as xrspatial        # numpy-backed DataArray in -> numpy-backed out
@@ -28,6 +29,7 @@ from .hillshade import hillshade  # noqa: F401
 from .multispectral import arvi, evi, nbr, ndvi, savi, sipi  # noqa: F401
 from .pathfinding import a_star_search  # noqa: F401
 from .perlin import perlin  # noqa: F401
+from .experimental.polygonize import polygonize  # noqa: F401
 from .proximity import (allocation, direction, euclidean_distance, great_circle_distance, manhattan_distance,  # noqa: F401
                         proximity)
 from .slope import slope  # noqa: F401
@@ -37,6 +39,6 @@ from .zonal import crosstab as zonal_crosstab  # noqa: F401
 from .zonal import regions  # noqa: F401
 from .zonal import stats as zonal_stats  # noqa: F401
 
-from . import analytics, classify, convolution, focal, local, multispectral, pathfinding, zonal  # noqa: F401
+from . import analytics, classify, convolution, experimental, focal, local, multispectral, pathfinding, zonal  # noqa: F401
 
 __version__ = "0.1.0"

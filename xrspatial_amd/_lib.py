@@ -182,6 +182,14 @@ _PROTOTYPES = {
     "xrs_astar": [c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int, c_int, c_int, c_int,
                   c_void_p, c_void_p, ctypes.POINTER(c_int64), c_void_p],
     "xrs_astar_tile_visits": [c_void_p, c_int64, c_int64, ctypes.POINTER(c_int64), c_void_p],
+    "xrs_polygonize_workspace_bytes": [c_int64, c_int64],
+    "xrs_polygonize_rings_workspace_bytes": [ctypes.c_uint64],
+    "xrs_polygonize_census": [c_void_p, c_int, c_void_p, c_int, c_int64, c_int64, c_int, c_void_p, ctypes.POINTER(ctypes.c_uint64),
+                              ctypes.POINTER(ctypes.c_uint64), c_void_p],
+    "xrs_polygonize_rings": [c_int64, c_int64, c_void_p, c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64),
+                             ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(c_int), c_void_p],
+    "xrs_polygonize_scatter": [c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, ctypes.c_uint64, ctypes.c_uint64,
+                               ctypes.c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "xrs_local_cells": [c_int, ctypes.POINTER(c_void_p), ctypes.POINTER(c_int), c_int, c_void_p, c_int, c_int64, c_void_p, c_int,
                         c_void_p],
     "xrs_local_combine_workspace_bytes": [c_int64, c_int],
@@ -204,7 +212,8 @@ _RESTYPES = {"xrs_kxk_workspace_bytes": c_size_t, "xrs_focal_workspace_bytes": c
              "xrs_geodesic_workspace_bytes": c_size_t, "xrs_classify_workspace_bytes": c_size_t,
              "xrs_regions_workspace_bytes": c_size_t, "xrs_viewshed_workspace_bytes": c_size_t,
              "xrs_proximity_workspace_bytes": c_size_t, "xrs_local_combine_workspace_bytes": c_size_t,
-             "xrs_astar_workspace_bytes": c_size_t}
+             "xrs_astar_workspace_bytes": c_size_t, "xrs_polygonize_workspace_bytes": c_size_t,
+             "xrs_polygonize_rings_workspace_bytes": c_size_t}
 
 EXPORTED = tuple(_PROTOTYPES)
 
