@@ -408,10 +408,15 @@ int xrs_zonal_majority_f64(const int32_t *zone_idx_dev, const double *values_dev
 /* majority WITHOUT a sort (csrc/zonal_mode.hip): the cells are routed zone by zone and then, inside a zone, by a hash
  * of the value's bits until every part fits an LDS hash table that counts multiplicities; same result as
  * xrs_zonal_majority_* (ties -> smallest value, -0.0 == +0.0, NaN for a zone without a valid cell) at ~1/6 of the traffic.
- * majority_dev holds n_zones + 1 doubles: the LAST one is the number of parts whose table overflowed (a zone of more
- * than ~2^27 cells of all-distinct values) -- nonzero means the results are not valid and the caller must use
- * xrs_zonal_majority_*.  n_zones <= xrs_zonal_mode_max_zones(); n < 2^31; `work_dev` holds
- * xrs_zonal_mode_workspace_bytes(n, n_zones, values_f64) bytes.  zone_counts_dev: the valid cells per zone as uint32 if the
+ * majority_dev holds n_zones + 1 doubles: the LAST one counts the threads that could not place a key because the table of
+ * their part was full -- nonzero means the results are not valid and the caller must use xrs_zonal_majority_*.  That
+ * depends on the DISTINCT values of a part, not on the size of the zone: a part overflows when more than 2048 of its
+ * distinct values share their slot of the count-only table with another cell.  Spread by the hash, that takes a zone of
+ * more than ~2^27 cells of all-distinct values; a few thousand values chosen to hash to one part do it in a zone of 6000
+ * cells.  n_zones <= xrs_zonal_mode_max_zones(); n < 2^31; `work_dev` holds
+ * xrs_zonal_mode_workspace_bytes(n, n_zones, values_f64) bytes and begins, after the call, with five uint32 that describe
+ * the plan it ran: n_valid (valid cells), n_parts (sum over the zones of their 2^B parts), n_chunks (8192-key chunks of
+ * the zones cut into parts), overflow (the count above) and n_direct (zones of more than 2^11 parts).  zone_counts_dev: the valid cells per zone as uint32 if the
  * caller has them (the `count` of xrs_zonal_partials_* for the same rasters and nodata value), else NULL -- they are
  * then counted here with one more pass over the rasters. */
 size_t xrs_zonal_mode_workspace_bytes(int64_t n, int n_zones, int values_f64);

@@ -22,9 +22,11 @@
 // 32 B / cell of streaming traffic instead of the sorts' ~100.  Grids of 4 / 6 / 7 are sized for the worst case the
 // plan can produce (no host round trip in the middle); surplus workgroups leave at once.
 //
-// A part that holds more DISTINCT keys than the table takes (only a zone of more than ~2^27 cells of continuous data,
-// where B is capped) raises the overflow count behind the results (majority_dev[n_zones]); the host then runs the
-// sorting path, which has no such limit.
+// A part in which more than SLOTS DISTINCT keys share their slot of the count-only table raises the overflow count behind
+// the results (majority_dev[n_zones]); the host then runs the sorting path, which has no such limit.  That is a matter of
+// the distinct keys of a part, not of the size of the zone: spread by the hash it takes a zone of more than ~2^27 cells of
+// continuous data (where B is capped), but part_of is a multiplication by an odd number and can be inverted -- a few
+// thousand values picked to land in one part overflow a zone of 6000 cells (tests/zonal_majority_cases.py: keys_in_part).
 #include "xrs_common.h"
 
 using namespace xrs;
