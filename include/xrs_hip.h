@@ -502,6 +502,30 @@ int xrs_viewshed_f32(const float *data_dev, int64_t rows, int64_t cols, int64_t 
 int xrs_viewshed_f64(const double *data_dev, int64_t rows, int64_t cols, int64_t view_row, int64_t view_col, double observer_elev,
                      double target_elev, double ew_res, double ns_res, void *work_dev, double *out_dev, void *stream);
 
+/* hillshade(shadows=True) (xrspatial/gpu_rtx/hillshade.py `_hillshade_rt` and gpu_rtx/mesh_utils.py `create_triangulation`,
+ * which trace the raster's triangle mesh through OptiX): replaced by one ray walk per cell over the same mesh, the result
+ * stated as a rule in DESIGN.md §6i and evaluated in float64.  data_dev: rows x cols C-contiguous, every cell finite (the caller
+ * checks).  scale: the reference's max(rows, cols) / max of the raster; zmin / zmax: bounds of the raster's values (the walk
+ * stops where a ray is above zmax * scale or below zmin * scale for good).  sun_*: the unit vector towards the sun, x along
+ * the columns, y along the rows.  shadows = 0 leaves the shadow rays out: Lambert's shade on the mesh's normals alone.
+ * out_dev (float32): the shade in [0, 1], halved where the cell's shadow ray hits the mesh; NaN on the border rows and columns.
+ * Two launches on the stream: the float32 vertex heights and a table of block maxima into work_dev
+ * (xrs_hillshade_shadow_workspace_bytes(rows, cols) bytes, caller-owned), then the walk.
+ * The probe entry points are for measuring (tools/hillshade_shadow_bench.py): the same walk with the block level over
+ * `block` x `block` cells (8, 16, 32; 0 = none; the entry points above use 32) and, where counts4_dev is not null, the
+ * { sum, max } of cells visited and { sum, max } of blocks tested per ray added into its four zeroed uint64. */
+size_t xrs_hillshade_shadow_workspace_bytes(int64_t rows, int64_t cols);
+int xrs_hillshade_shadow_f32(const float *data_dev, int64_t rows, int64_t cols, double scale, double zmin, double zmax, double sun_x,
+                             double sun_y, double sun_z, int shadows, void *work_dev, float *out_dev, void *stream);
+int xrs_hillshade_shadow_f64(const double *data_dev, int64_t rows, int64_t cols, double scale, double zmin, double zmax, double sun_x,
+                             double sun_y, double sun_z, int shadows, void *work_dev, float *out_dev, void *stream);
+int xrs_hillshade_shadow_probe_f32(const float *data_dev, int64_t rows, int64_t cols, double scale, double zmin, double zmax,
+                                   double sun_x, double sun_y, double sun_z, int block, void *work_dev, float *out_dev,
+                                   uint64_t *counts4_dev, void *stream);
+int xrs_hillshade_shadow_probe_f64(const double *data_dev, int64_t rows, int64_t cols, double scale, double zmin, double zmax,
+                                   double sun_x, double sun_y, double sun_z, int block, void *work_dev, float *out_dev,
+                                   uint64_t *counts4_dev, void *stream);
+
 /* proximity / allocation / direction (xrspatial/proximity.py `_process`): for every cell of a rows x cols C-contiguous raster
  * (`dtype`: XRS_DT_*) the exact nearest target, with the reference's float64 distance arithmetic rounded to float32, the
  * sweep's order among equidistant targets and its max_distance cut.

@@ -1,12 +1,36 @@
-"""xrspatial.hillshade drop-in.  Reference: xrspatial/hillshade.py:103-208."""
+"""xrspatial.hillshade drop-in.  Reference: xrspatial/hillshade.py:103-208.
+
+`shadows=True` is the reference's ray-traced path (gpu_rtx/hillshade.py, gpu_rtx/mesh_utils.py: OptiX on NVIDIA RT cores)
+as a rule, evaluated by csrc/hillshade_shadow.hip with one ray walk per cell.  Everything is float64 unless
+marked; only + - * /, sqrt and comparisons, every sum left to right:
+  1 sun     (sin(az) cos(alt), -cos(az) cos(alt), sin(alt)), az / alt in radians (`_get_sun_dir`); x is the column, y the row.
+            Any angle, at or below the horizon too.
+  2 mesh    vertex (w, h, zv[h, w]), zv = (float32)((double)value * scale), scale = max(H, W) / max of the raster; every cell
+            with h < H - 1, w < W - 1 carries T0 = [(h+1, w), (h+1, w+1), (h, w)] and T1 = [(h+1, w+1), (h, w+1), (h, w)].
+  3 hit     interior cells only: x0 = (double)(float)(j + 1e-3), y0 likewise from i (the float32 camera origin), fx = x0 - j,
+            fy = y0 - i; the point is in T0 when fy >= fx, else T1; with C, D = zv[i, j], zv[i, j+1] and A, B = zv[i+1, j],
+            zv[i+1, j+1] the plane's gradient is (gx, gy) = (B - A, A - C) in T0, (D - C, B - D) in T1; zh = C + fx gx + fy gy;
+            n = (-gx, -gy, 1) / sqrt(gx^2 + gy^2 + 1), the reference's flipped normal.  Computed, not traced.
+  4 shadow  origin (x0, y0, zh) + n * 1e-3, direction sun; in shadow when any triangle of the mesh is hit with t > 1e-3, by
+            Moller-Trumbore: e1 = v1 - v0, e2 = v2 - v0, p = d x e2, det = e1 . p, s = o - v0, u = (s . p) / det, q = s x e1,
+            v = (d . q) / det, t = (e2 . q) / det; hit iff det != 0, u >= 0, v >= 0, u + v <= 1, t > 1e-3.  A face turned away
+            from the sun shadows itself through its own triangle, as in the reference.
+  5 shade   (sun . n + 1) / 2, halved in shadow, clamped to [0, 1], float32; NaN on rows 0, H - 1 and columns 0, W - 1.
+  6 inputs  2-D, NumPy- or DeviceArray-backed (the result's backend, float32); float32 / float64 read in place, other dtypes
+            through float64.  A non-finite cell or a maximum <= 0 raises ValueError (the reference's scale is NaN or negative
+            there); H < 3 or W < 3 gives all NaN; dask, ShardedArray and fuse() scopes raise NotImplementedError.
+Departures from the reference: the camera hit is computed (its camera at height 10000 is inside the terrain from
+max(H, W) = 10000 on), non-finite rasters are refused, and the trace is float64.  There is no CPU fallback.
+"""
 from __future__ import annotations
 
+import math
 from typing import Optional
 
 import numpy as np
 
-from . import fused
-from ._launch import stencil
+from . import _lib, fused
+from ._launch import finish, get_stream, stencil
 from ._xr import DataArray
 from .dataset_support import supports_dataset
 from .device import DeviceArray
@@ -33,6 +57,80 @@ def _hill(data, out_dtype, azimuth, angle_altitude):
                    pre=(int(np.dtype(out_dtype) == np.float64),))
 
 
+# ------------------------------------------------------------------ shadows=True (module docstring)
+_SUFFIX = {np.dtype(np.float32): "f32", np.dtype(np.float64): "f64"}
+
+
+def sun_vector(azimuth, angle_altitude):
+    """rule 1: the unit vector towards the sun (gpu_rtx/hillshade.py:133-143 `_get_sun_dir`, without the rotations)"""
+    az, alt = math.radians(float(azimuth)), math.radians(float(angle_altitude))
+    return math.sin(az) * math.cos(alt), -math.cos(az) * math.cos(alt), math.sin(alt)
+
+
+def _height_scale(count, cells, zmin, zmax, rows, cols):
+    """rule 6's refusals and rule 2's scale from { count, min, max } of the finite cells"""
+    if int(count) != cells:
+        raise ValueError(f"hillshade(shadows=True): the raster holds {cells - int(count)} non-finite cells")
+    if not zmax > 0:
+        raise ValueError(f"hillshade(shadows=True): the raster's maximum must be positive, got {zmax}")
+    scale = float(max(rows, cols)) / zmax                    # mesh_utils.py:17-19
+    if not (math.isfinite(scale) and scale > 0):
+        raise ValueError(f"hillshade(shadows=True): the raster's maximum {zmax} gives no usable height scale")
+    return scale
+
+
+def _run_shadows(data, azimuth, angle_altitude, shadows=1):
+    """A NumPy raster gets NumPy back, a DeviceArray a DeviceArray; float32 either way."""
+    sun = sun_vector(azimuth, angle_altitude)
+    if not all(math.isfinite(v) for v in sun):
+        raise ValueError("hillshade: azimuth and angle_altitude must be finite")
+    like_numpy = isinstance(data, np.ndarray)
+    rows, cols = data.shape
+    stream = get_stream()
+    if like_numpy:                                           # a host raster is checked where it lies, before any device work
+        if np.dtype(data.dtype) not in _SUFFIX:              # integers, bool, float16: float64, as viewshed reads them
+            data = data.astype(np.float64)
+        count = int(np.isfinite(data).sum())
+        zmin, zmax = (float(data.min()), float(data.max())) if count == data.size else (math.nan, math.nan)
+        scale = _height_scale(count, data.size, zmin, zmax, rows, cols)
+        _lib.require_device()
+        src = DeviceArray.from_numpy(np.ascontiguousarray(data), stream=stream)
+    else:
+        _lib.require_device()
+        src = data if np.dtype(data.dtype) in _SUFFIX else DeviceArray.from_numpy(data.get(stream).astype(np.float64), stream=stream)
+        suffix = _SUFFIX[np.dtype(src.dtype)]
+        stats = DeviceArray((4,), np.float64)                # { count, min, max, sum } of the finite cells, one pass
+        work = DeviceArray((int(_lib.load().xrs_classify_workspace_bytes(1, int(suffix == "f64"))),), np.uint8)
+        _lib.call("xrs_classify_finite_stats_" + suffix, src.ptr, rows * cols, work.ptr, stats.ptr, stream)
+        count, zmin, zmax, _ = (float(v) for v in stats.get(stream))
+        scale = _height_scale(count, rows * cols, zmin, zmax, rows, cols)
+    out = DeviceArray((rows, cols), np.float32)
+    work = DeviceArray((int(_lib.load().xrs_hillshade_shadow_workspace_bytes(rows, cols)),), np.uint8)
+    _lib.call("xrs_hillshade_shadow_" + _SUFFIX[np.dtype(src.dtype)], src.ptr, rows, cols, scale, zmin, zmax, sun[0], sun[1], sun[2],
+              int(shadows), work.ptr, out.ptr, stream)
+    if not like_numpy:
+        _lib.call("xrs_stream_sync", stream)                 # the workspace goes back to the pool when this returns
+    return finish(out, like_numpy)
+
+
+def _hillshade_shadows(agg, azimuth, angle_altitude, name):
+    if len(agg.shape) != 2:
+        raise ValueError(f"hillshade(shadows=True): a 2-D raster is needed, got {len(agg.shape)} dimensions")
+    if 0 in agg.shape:
+        raise ValueError(f"hillshade(shadows=True): an empty raster, shape {tuple(agg.shape)}")
+    if fused.current() is not None:
+        raise NotImplementedError("hillshade(shadows=True) cannot join a fuse() scope: a shadow ray reads cells far from its "
+                                  "own, and the fused pass hands every product one row strip at a time")
+    if isinstance(agg.data, ShardedArray):
+        raise NotImplementedError("hillshade(shadows=True) does not support row-sharded (multi-GPU) DataArray: rays cross shards")
+    if is_dask(agg.data):
+        raise NotImplementedError("hillshade(shadows=True) does not support dask backed DataArray: rays cross chunks")
+    if not isinstance(agg.data, (np.ndarray, DeviceArray)):
+        raise TypeError('Unsupported Array Type: {}'.format(type(agg.data)))
+    out = _run_shadows(agg.data, azimuth, angle_altitude)
+    return DataArray(out, name=name, coords=agg.coords, dims=agg.dims, attrs=agg.attrs)
+
+
 @supports_dataset
 def hillshade(agg: DataArray,
               azimuth: int = 225,
@@ -42,11 +140,12 @@ def hillshade(agg: DataArray,
     """Illumination of every cell for a light at `azimuth` / `angle_altitude` (degrees), in [0, 1].
 
     Same signature and results as `xrspatial.hillshade`; runs on the MI355X.
-    `shadows=True` needs the reference's OptiX ray tracer (NVIDIA RT cores) and
-    raises RuntimeError here exactly as upstream does without rtxpy.
+    `shadows=True` shades the reference's triangle mesh instead and halves the value of every cell whose ray towards the
+    sun hits the mesh (what upstream traces through OptiX; the rule is in this module's docstring): float32, NumPy- or
+    DeviceArray-backed rasters without non-finite cells and with a positive maximum.
     """
     if shadows:
-        raise RuntimeError("Can only calculate shadows if cupy and rtxpy are available")
+        return _hillshade_shadows(agg, azimuth, angle_altitude, name)
     scope = fused.current()
     if scope is not None:
         return scope.defer('hillshade', agg, name, {'light': (float(azimuth), float(angle_altitude))},
