@@ -634,6 +634,22 @@ int xrs_local_combine(const void *const *planes, const int *dtypes, int n_planes
 int xrs_local_gather(const void *const *planes, const int *dtypes, int n_planes, int64_t n, const unsigned *cells_dev,
                      int64_t n_cells, void *out_dev, void *stream);
 
+/* natural_breaks (xrspatial/classify.py:508-564 `_run_numpy_jenks_matrices`): the two (n + 1) x (k + 1) row-major float32 tables
+ * of the Jenks dynamic programme over a sorted float32 sample of n values (1 <= n < 2^24, the limits being float32 row numbers)
+ * and k >= 1 classes, initial values included: row 0 and column 0 zero, lower_class_limits[1][1:] = 1, var_combinations[2:][1:] =
+ * inf where the sweep leaves them.  Bit for bit the reference's loop: float64 running sums of the float32 values and of their
+ * float32 squares, one IEEE float64 division per step, the float32 minimum replaced on `>=`.  One launch for
+ * the initial tables, then one per column 1 .. k, one thread per row 2 .. n; n == 1 launches the first only.  work_dev:
+ * xrs_jenks_workspace_bytes(n, k) bytes, caller-owned (two contiguous working columns; 0 for arguments the call refuses).
+ *   xrs_gather_elems  out_dev[i] = in_dev[idx_dev[i]] for n_idx uint32 indices into n elements of elem_size 1, 2, 4 or 8 bytes,
+ *                     copied without conversion (the sample of natural_breaks in the raster's own dtype); an index >= n gives
+ *                     zero bytes. */
+size_t xrs_jenks_workspace_bytes(int64_t n, int k);
+int xrs_jenks_matrices_f32(const float *sorted_dev, int64_t n, int k, float *lower_class_limits_dev, float *var_combinations_dev,
+                           void *work_dev, size_t work_bytes, void *stream);
+int xrs_gather_elems(const void *in_dev, int elem_size, int64_t n, const uint32_t *idx_dev, int64_t n_idx, void *out_dev,
+                     void *stream);
+
 /* multispectral.true_color (xrspatial/multispectral.py:1334-1495).
  *   xrs_nan_minmax_f32: minmax_dev[0..1] = np.nanmin / np.nanmax of a float32 plane (NaN, NaN if it holds no number);
  *   xrs_true_color_u8:  rgba[i] = { stretch(red), stretch(green), stretch(blue), alpha } with

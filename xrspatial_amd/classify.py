@@ -6,8 +6,9 @@ finite min / max / count / sum and moment reductions, the exact order statistics
 maximum_breaks.  What crosses to the host is a handful of scalars; from them the reference's own host formulas --
 restated below, quirks included -- build the bins, and the bin pass runs on the raster already resident in HBM.
 
-`natural_breaks` is not provided.  dask- and ShardedArray-backed rasters are accepted by the per-cell
-`binary` and `reclassify` only; the statistic-driven classifiers raise NotImplementedError for them.
+`natural_breaks` lives in jenks.py and is exported as `xrspatial_amd.natural_breaks`.  dask- and ShardedArray-backed
+rasters are accepted by the per-cell `binary` and `reclassify` only; the statistic-driven classifiers raise
+NotImplementedError for them.
 """
 from __future__ import annotations
 
