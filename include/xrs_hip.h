@@ -225,6 +225,14 @@ int xrs_focal_stats_f32_ex(const float *in_dev, float *const *outs_dev, unsigned
  * with the separable walk's within the documented tolerance (float32 walker vs float64 column sums: ~2e-6 relative on var / std),
  * not bit for bit. */
 size_t xrs_focal_workspace_bytes(int64_t rows, int64_t cols, int krows, int kcols);
+/* For tests: which kernels served the calling thread's LAST xrs_focal_stats_f32 / xrs_focal_stats_f32_ex /
+ * xrs_convolve2d_f32 call, as text, one item per launch group in launch order, joined by ';'.  An item is a walker's name
+ * (focal_mom_circle, wide_annulus7, focal_ext_annulus_a, focal_box_f32, focal_mean_runs, boxsep ...) or a branch of the
+ * dispatch (big, pass, strips3, strips5, lds_mean7, tap0 .. tap4, conv_strips3, conv_strips5, conv_tap) with (R) or
+ * (R,RI), and for the strip walkers the tiling the launch chose: [wave=<wave-tile columns>,wg=<workgroup columns>,
+ * rows=<tile rows>,grid=<workgroups across>x<down>].  Empty after a call that launched nothing.  Returns the length of
+ * the text (as snprintf); at most buflen - 1 bytes and a NUL are written. */
+int xrs_debug_window_route(char *buf, size_t buflen);
 
 /* focal.apply with a user callable (func other than the built-in reducers): the kernel-shaped float32 arrays that
  * _apply_numpy, xrspatial/focal.py:305-326, builds per cell (NaN, then data[ky, kx] where kernel == 1 and inside the

@@ -15,6 +15,8 @@ from tests import classify_oracle as corc
 from xrspatial_amd import classify as cl
 
 _live = {}      # address -> ctypes buffer (keeps "device" allocations alive)
+_route = [""]   # what xrs_debug_window_route answers: the last window call, served by the oracle
+_WINDOW_CALLS = ("xrs_focal_stats_f32", "xrs_focal_stats_f32_ex", "xrs_convolve2d_f32")
 
 
 def _arr(ptr, n, dtype):
@@ -51,6 +53,8 @@ def _kernel(ptr, kr, kc):
 
 
 def call(name, *a):
+    if name in _WINDOW_CALLS:
+        _route[0] = "oracle:" + name
     if name == "xrs_malloc":
         buf = ctypes.create_string_buffer(max(int(a[1]), 16) + 64)
         addr = (ctypes.addressof(buf) + 63) // 64 * 64
@@ -339,6 +343,12 @@ class _FakeLib:
     @staticmethod
     def xrs_focal_workspace_bytes(rows, cols, kr, kc):
         return 16
+
+    @staticmethod
+    def xrs_debug_window_route(buf, buflen):
+        text = _route[0].encode()
+        ctypes.memmove(buf, text[:max(int(buflen) - 1, 0)] + b"\0", min(len(text) + 1, int(buflen)))
+        return len(text)
 
     @staticmethod
     def xrs_zonal_majority_workspace_bytes(n, nz, f64):

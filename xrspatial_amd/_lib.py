@@ -99,6 +99,7 @@ _PROTOTYPES = {
     "xrs_focal_stats_f32_ex": [c_void_p, ctypes.POINTER(c_void_p), c_uint, c_int64, c_int64, c_int64, c_int64,
                                c_void_p, c_int, c_int, c_void_p, c_size_t, c_int, c_int, c_uint, c_void_p],
     "xrs_focal_workspace_bytes": [c_int64, c_int64, c_int, c_int],
+    "xrs_debug_window_route": [c_void_p, c_size_t],
     "xrs_focal_mean3x3_passes": [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p, c_int, c_void_p],
     "xrs_focal_mean3x3": [c_void_p, c_int, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int,
                           c_int, c_int, c_void_p],
@@ -257,6 +258,13 @@ def load():
 def last_error() -> str:
     buf = ctypes.create_string_buffer(512)
     load().xrs_last_error(buf, 512)
+    return buf.value.decode(errors="replace")
+
+
+def window_route() -> str:
+    """Which kernels served this thread's last focal / convolve_2d window call (xrs_debug_window_route); for tests."""
+    buf = ctypes.create_string_buffer(1024)
+    load().xrs_debug_window_route(buf, 1024)
     return buf.value.decode(errors="replace")
 
 

@@ -515,6 +515,7 @@ int launch_box_sep(const float *in, float *out_sum, float *out_mean, float *out_
     XRS_HIP(hipMemsetAsync(todo, 0, (size_t)(fb_groups_x * fb_tiles_y), s));
     hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(256), lds, s, a);
     XRS_LAUNCH_CHECK();
+    route_note("boxsep", a.ry, -1, a.w_out, 4 * a.w_out, a.tile_rows, a.groups_x, a.tiles_y);
     return 0;
 }
 

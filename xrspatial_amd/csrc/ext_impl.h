@@ -309,6 +309,7 @@ int launch_ext(ExtArgs &a, hipStream_t s) {
     if (n_out == 3) hipLaunchKernelGGL((focal_ext_kernel<R, Shape, 3>), dim3((unsigned)grid), dim3(256), 0, s, a);
     else hipLaunchKernelGGL((focal_ext_kernel<R, Shape, 1>), dim3((unsigned)grid), dim3(256), 0, s, a);
     XRS_LAUNCH_CHECK();
+    route_note(XRS_STR(XRS_EXT_ENTRY), R, Shape::hwi(R, 0), 64, 256, a.tile_rows, g.tiles_x, g.n_tiles / g.tiles_x);
     return 0;
 }
 

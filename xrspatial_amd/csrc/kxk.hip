@@ -917,6 +917,12 @@ int allow_big_lds(K kernel_fn, size_t lds) {
     return 0;
 }
 
+// route witness (xrs_common.h) for the branches of this file: `tag` served the call if its launch went through
+int noted(int rc, const char *tag, int R = -1) {
+    if (rc == 0) route_note(tag, R);
+    return rc;
+}
+
 template <int KH, int KW, int MODE>
 int launch_focal(const KxkArgs &a, bool vec, size_t lds, hipStream_t s) {
     const unsigned grid = (unsigned)xcd_grid(a.n_tiles, XCD_UNIT(XRS_XCD_LDS, a.tiles_x));
@@ -926,7 +932,7 @@ int launch_focal(const KxkArgs &a, bool vec, size_t lds, hipStream_t s) {
     else
         hipLaunchKernelGGL((focal_stats_kernel<KH, KW, MODE, false>), dim3(grid), dim3(256), lds, s, a);
     XRS_LAUNCH_CHECK();
-    return 0;
+    return noted(0, MODE == 0 ? "tap0" : MODE == 1 ? "tap1" : MODE == 2 ? "tap2" : MODE == 3 ? "tap3" : "tap4", a.krows / 2);
 }
 
 template <int KH, int KW>
@@ -1049,10 +1055,10 @@ const WalkerFamily mom_walk = {try_launch_focal_mom_circle, try_launch_focal_mom
 template <bool MEAN_ONLY>
 int dispatch_focal(const KxkArgs &a, bool vec, size_t lds, hipStream_t s) {
     // (the register-strip kernels take any width / pitch / base address; `vec` only gates the LDS-tile kernels)
-    if (a.krows == 3 && a.kcols == 3) return MEAN_ONLY ? launch_mean_direct<3, 3>(a, s) : launch_stats_direct<3, 3>(a, s);
-    if (a.krows == 5 && a.kcols == 5) return MEAN_ONLY ? launch_mean_direct<5, 5>(a, s) : launch_stats_direct<5, 5>(a, s);
+    if (a.krows == 3 && a.kcols == 3) return noted(MEAN_ONLY ? launch_mean_direct<3, 3>(a, s) : launch_stats_direct<3, 3>(a, s), "strips3", 1);
+    if (a.krows == 5 && a.kcols == 5) return noted(MEAN_ONLY ? launch_mean_direct<5, 5>(a, s) : launch_stats_direct<5, 5>(a, s), "strips5", 2);
     // (7x7 would need 256 VGPRs in registers: it stays on the LDS-tile kernel)
-    if (MEAN_ONLY && vec && a.th == TH_FAST && a.krows == 7 && a.kcols == 7) return launch_mean_fast<7, 7>(a, lds, s);
+    if (MEAN_ONLY && vec && a.th == TH_FAST && a.krows == 7 && a.kcols == 7) return noted(launch_mean_fast<7, 7>(a, lds, s), "lds_mean7", 3);
     return launch_focal<0, 0, MEAN_ONLY ? 0 : 1>(a, vec, lds, s);
 }
 
@@ -1075,14 +1081,15 @@ size_t xrs_focal_workspace_bytes(int64_t rows, int64_t cols, int krows, int kcol
 int xrs_convolve2d_f32(const float *in_dev, float *out_dev, int64_t rows, int64_t cols, int64_t ld_in,
                        int64_t ld_out, const double *kernel, int krows, int kcols, void *work_dev,
                        int halo_top, int halo_bot, void *stream) {
+    route_clear();
     if (int rc = check_common("xrs_convolve2d_f32", in_dev, rows, cols, ld_in, ld_out, kernel, krows, kcols,
                               halo_top, halo_bot)) return rc;
     if (!out_dev || !work_dev) return fail("xrs_convolve2d_f32: null output/workspace");
     if (rows == 0 || cols == 0) return 0;
     if (krows > MAX_K || kcols > MAX_K) {
         float *outs1[1] = {out_dev};
-        return launch_window_any_size(true, in_dev, outs1, rows, cols, ld_in, ld_out, kernel, krows, kcols, work_dev, halo_top,
-                                      halo_bot, as_stream(stream));
+        return noted(launch_window_any_size(true, in_dev, outs1, rows, cols, ld_in, ld_out, kernel, krows, kcols, work_dev, halo_top,
+                                            halo_bot, as_stream(stream)), "big", krows / 2);
     }
     KxkArgs a;
     memset(&a, 0, sizeof(a));
@@ -1106,20 +1113,21 @@ int xrs_convolve2d_f32(const float *in_dev, float *out_dev, int64_t rows, int64_
     if (const int rc = launch_by_shape(wide_conv, c); rc >= 0) return rc;
     a.tiles_x = (cols + TW - 1) / TW;
     a.n_tiles = a.tiles_x * ((rows + a.th - 1) / a.th);
-    if (krows == 3 && kcols == 3) return launch_convolve_direct<3, 3>(a, s);
-    if (krows == 5 && kcols == 5) return launch_convolve_direct<5, 5>(a, s);
+    if (krows == 3 && kcols == 3) return noted(launch_convolve_direct<3, 3>(a, s), "conv_strips3", 1);
+    if (krows == 5 && kcols == 5) return noted(launch_convolve_direct<5, 5>(a, s), "conv_strips5", 2);
     const unsigned grid = (unsigned)xcd_grid(a.n_tiles, XCD_UNIT(XRS_XCD_LDS, a.tiles_x));
     const bool vec = vec_ok(a, 1u);
     if (int rc = vec ? allow_big_lds(&convolve_kernel<0, 0, true>, lds) : allow_big_lds(&convolve_kernel<0, 0, false>, lds)) return rc;
     if (vec) hipLaunchKernelGGL((convolve_kernel<0, 0, true>), dim3(grid), dim3(256), lds, s, a);
     else hipLaunchKernelGGL((convolve_kernel<0, 0, false>), dim3(grid), dim3(256), lds, s, a);
     XRS_LAUNCH_CHECK();
-    return 0;
+    return noted(0, "conv_tap", krows / 2);
 }
 
 int xrs_focal_stats_f32(const float *in_dev, float *const *outs_dev, unsigned stat_mask, int64_t rows,
                         int64_t cols, int64_t ld_in, int64_t ld_out, const double *kernel, int krows,
                         int kcols, void *work_dev, int halo_top, int halo_bot, void *stream) {
+    route_clear();
     return xrs_focal_stats_f32_ex(in_dev, outs_dev, stat_mask, rows, cols, ld_in, ld_out, kernel, krows, kcols, work_dev,
                                   work_dev ? xrs_kxk_workspace_bytes(krows, kcols) : 0, halo_top, halo_bot, 0u, stream);
 }
@@ -1135,6 +1143,7 @@ int xrs_focal_stats_f32(const float *in_dev, float *const *outs_dev, unsigned st
 //   A    4-12   sum, mean + sum                 a sum        moments walker
 //   C B A 4-12  anything beyond mean / sum      no EXACT     extrema walker (max / min / range) + moments walker (the rest; B with
 //                                                            a workspace: boxsep in front); SEQ: the sum from the f32 column walker
+//                                                            (C B) or the LDS-tile tap walk (A)
 //   C B  3-12   mean                            (EXACT)      f64 column walker
 //   any K*K>49  mean                                         prefix-sum run kernel
 //   any K*K>49  several                                      mean / var / std: f64 column walker (C B 2-12), else run kernel;
@@ -1152,6 +1161,7 @@ int xrs_focal_stats_f32_ex(const float *in_dev, float *const *outs_dev, unsigned
                            int64_t cols, int64_t ld_in, int64_t ld_out, const double *kernel, int krows,
                            int kcols, void *work_dev, size_t work_bytes, int halo_top, int halo_bot, unsigned flags,
                            void *stream) {
+    route_clear();
     if (int rc = check_common("xrs_focal_stats_f32", in_dev, rows, cols, ld_in, ld_out, kernel, krows, kcols,
                               halo_top, halo_bot)) return rc;
     if (!outs_dev) return fail("xrs_focal_stats_f32: null outputs");
@@ -1171,8 +1181,8 @@ int xrs_focal_stats_f32_ex(const float *in_dev, float *const *outs_dev, unsigned
     hipStream_t s = c.s;
     if (krows > MAX_K || kcols > MAX_K) {
         if (!work_dev || work_bytes < xrs_kxk_workspace_bytes(krows, kcols)) return fail("xrs_focal_stats_f32: windows beyond 63x63 need a workspace of xrs_kxk_workspace_bytes()");
-        return launch_window_any_size(false, in_dev, c.out, rows, cols, ld_in, ld_out, kernel, krows, kcols, work_dev, halo_top,
-                                      halo_bot, s);
+        return noted(launch_window_any_size(false, in_dev, c.out, rows, cols, ld_in, ld_out, kernel, krows, kcols, work_dev, halo_top,
+                                            halo_bot, s), "big", krows / 2);
     }
     const WorkspaceLayout w = workspace_layout(rows, cols, krows, kcols);
     if (work_dev && work_bytes >= w.bytes) {
@@ -1193,6 +1203,7 @@ int xrs_focal_stats_f32_ex(const float *in_dev, float *const *outs_dev, unsigned
     const unsigned f64_stats = m_mean | (1u << XRS_STAT_VAR) | (1u << XRS_STAT_STD);
     const unsigned mm_stats = (1u << XRS_STAT_MAX) | (1u << XRS_STAT_MIN) | (1u << XRS_STAT_RANGE);
     c.mask = recognise_mask(kernel, krows, kcols, false);
+    bool sum_by_taps = false;
     if (!gen1 && !(stat_mask & ~(m_mean | m_sum)) && !((stat_mask & m_sum) && seq_sum)) {
         // mean and / or sum only: one 16-byte load per lane and row, float32 prefix sums (wide_impl.h).  Annuli: the wide walker
         // has the mean alone (a row with a hole = two runs); with the sum, the moments walker with only those planes
@@ -1205,7 +1216,9 @@ int xrs_focal_stats_f32_ex(const float *in_dev, float *const *outs_dev, unsigned
         // several statistics: the extrema walker (ext_impl.h: max / min / range) and the moments walker (mom_impl.h: mean /
         // var / std / sum), each one pass, back to back on the one stream (two streams, forked / joined by events, measured no
         // faster: 2.39 vs 2.43 ms in round 3; 2.14 - 2.23 vs 2.19 in round 4: profiles/r04/ab_two_streams.log); a sequential
-        // `sum` comes from its own kernel.
+        // `sum` comes from its own kernel: the float32 column walker (circles, boxes), or -- annuli, which have no column
+        // walker -- the LDS-tile tap walk below that also serves `sum` alone on such a mask (`sum_by_taps`; nothing between
+        // here and that launch can fail: plan_tile holds for every window up to MAX_K).
         const WindowCall c_mom = seq_sum ? with_outputs(c, ~m_sum) : c;
         int rc = 0;
         if (stat_mask & mm_stats) rc = launch_by_shape(ext_walk, c);
@@ -1215,7 +1228,7 @@ int xrs_focal_stats_f32_ex(const float *in_dev, float *const *outs_dev, unsigned
             if (!(seq_sum && c.out[XRS_STAT_SUM])) return 0;
             const int rc2 = launch_by_shape(walk_f32, with_outputs(c, m_sum));
             if (rc2 >= 0) return rc2;
-            return fail("xrs_focal_stats_f32: no sequential-sum kernel for this mask");
+            sum_by_taps = true;
         }
         // (rc < 0: no circle, box or annulus of radius 4..12 -- the kernels below)
     }
@@ -1250,6 +1263,10 @@ int xrs_focal_stats_f32_ex(const float *in_dev, float *const *outs_dev, unsigned
 
     a.tiles_x = (cols + TW - 1) / TW;
     a.n_tiles = a.tiles_x * ((rows + a.th - 1) / a.th);
+    if (sum_by_taps) {
+        for (int i = 0; i < XRS_NUM_STATS; ++i) if (i != XRS_STAT_SUM) a.out[i] = nullptr;
+        return launch_focal<0, 0, 3>(a, vec_ok(a, m_sum), lds, s);
+    }
     const bool vec = vec_ok(a, stat_mask);
     if (stat_mask != m_mean && krows * kcols > 49) {
         // large run-structured masks, several statistics: mean / var / std from the float64 column walker (circles, boxes) or
@@ -1273,8 +1290,8 @@ int xrs_focal_stats_f32_ex(const float *in_dev, float *const *outs_dev, unsigned
     if (stat_mask == m_mean && pass_has_compile_time_mask(kernel, krows, kcols)) {
         // circle_kernel(1, 1, 2) / np.ones((3, 3)): the strip kernel of pass.hip without terrain products -- compile-time
         // mask, shared row sums
-        return xrs_raster_pass_f32(in_dev, nullptr, nullptr, nullptr, nullptr, a.out[XRS_STAT_MEAN], kernel, krows, kcols, work_dev,
-                                   rows, cols, ld_in, ld_out, 1.0, 1.0, 0.0, 0.0, halo_top, halo_bot, stream);
+        return noted(xrs_raster_pass_f32(in_dev, nullptr, nullptr, nullptr, nullptr, a.out[XRS_STAT_MEAN], kernel, krows, kcols, work_dev,
+                                         rows, cols, ld_in, ld_out, 1.0, 1.0, 0.0, 0.0, halo_top, halo_bot, stream), "pass", krows / 2);
     }
     if (stat_mask == m_mean) return dispatch_focal<true>(a, vec, lds, s);
     if (c.mask.R == 2 || c.mask.R == 3) {
@@ -1289,6 +1306,34 @@ int xrs_focal_stats_f32_ex(const float *in_dev, float *const *outs_dev, unsigned
     }
     // the all-statistics kernel always produces the mean internally; give it somewhere to go
     return dispatch_focal<false>(a, vec, lds, s);
+}
+
+// The route of this thread's last xrs_focal_stats_f32(_ex) / xrs_convolve2d_f32 call (xrs_common.h), items joined by ';':
+// name(R) or name(R,RI), and behind it [wave=..,wg=..,rows=..,grid=XxY] for the launches that report their tiling.
+// Returns the length of the full text (as snprintf), at most buflen - 1 bytes of which are written.
+int xrs_debug_window_route(char *buf, size_t buflen) {
+    const Route &r = route();
+    char text[1024];
+    size_t n = 0;
+    text[0] = 0;
+    for (int i = 0; i < r.n && n < sizeof(text); ++i) {
+        const RouteItem &it = r.item[i];
+        n += snprintf(text + n, sizeof(text) - n, "%s%s", i ? ";" : "", it.name);
+        if (n < sizeof(text) && it.R >= 0) {
+            if (it.RI >= 0) n += snprintf(text + n, sizeof(text) - n, "(%d,%d)", it.R, it.RI);
+            else n += snprintf(text + n, sizeof(text) - n, "(%d)", it.R);
+        }
+        if (n < sizeof(text) && it.wave_cols)
+            n += snprintf(text + n, sizeof(text) - n, "[wave=%d,wg=%d,rows=%d,grid=%ldx%ld]", it.wave_cols, it.wg_cols, it.tile_rows,
+                          it.wgs_x, it.wgs_y);
+    }
+    if (n >= sizeof(text)) n = sizeof(text) - 1;
+    if (buf && buflen) {
+        const size_t m = n < buflen - 1 ? n : buflen - 1;
+        memcpy(buf, text, m);
+        buf[m] = 0;
+    }
+    return (int)n;
 }
 
 int xrs_focal_mean3x3(const void *in_dev, int in_is_f64, double *out_dev, int64_t rows, int64_t cols,

@@ -409,8 +409,10 @@ static int launch_runs_for(const WindowCall &c, bool with_var) {
     if (with_var) { a.out_var = c.out[XRS_STAT_VAR]; a.out_std = c.out[XRS_STAT_STD]; }
     a.rows = c.rows; a.cols = c.cols; a.ld_in = c.ld_in; a.ld_out = c.ld_out;
     a.halo_top = c.halo_top; a.halo_bot = c.halo_bot;
-    if (with_var) return launch_runs(focal_meanvar_runs_kernel, a, 2 * sizeof(double) + sizeof(int), c.s);
-    return launch_runs(focal_mean_runs_kernel, a, sizeof(double) + sizeof(int), c.s);
+    const int rc = with_var ? launch_runs(focal_meanvar_runs_kernel, a, 2 * sizeof(double) + sizeof(int), c.s)
+                            : launch_runs(focal_mean_runs_kernel, a, sizeof(double) + sizeof(int), c.s);
+    if (rc == 0) route_note(with_var ? "focal_meanvar_runs" : "focal_mean_runs", c.krows / 2);
+    return rc;
 }
 int try_launch_focal_mean_runs(const WindowCall &c) { return launch_runs_for(c, false); }
 // same tiles, plus variance / standard deviation from a second prefix array (any output may be null)

@@ -855,6 +855,7 @@ int launch_mom(MomArgs &a, const WindowCall &c) {
         hipLaunchKernelGGL((focal_mom_exact_kernel<R, Shape>), dim3((unsigned)(cus * 2)), dim3(256), 0, s, a);
         XRS_LAUNCH_CHECK();
     }
+    route_note(XRS_STR(XRS_MOM_ENTRY), R, Shape::hwi(R, 0), C::TW, 4 * C::TW, a.tile_rows, a.groups_x, tiles_y);
     return 0;
 }
 

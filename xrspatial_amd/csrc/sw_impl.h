@@ -414,6 +414,7 @@ int launch_sw(SwArgs &a, hipStream_t s) {
     if (n_out == XRS_NUM_STATS) hipLaunchKernelGGL((focal_sw_kernel<R, Shape, NC, XRS_NUM_STATS>), dim3((unsigned)grid), dim3(256), 0, s, a);
     else hipLaunchKernelGGL((focal_sw_kernel<R, Shape, NC, 1>), dim3((unsigned)grid), dim3(256), 0, s, a);
     XRS_LAUNCH_CHECK();
+    route_note(XRS_STR(XRS_SW_ENTRY), R, -1, C::TW, 4 * C::TW, a.tile_rows, a.groups_x, a.tiles_y);
     return 0;
 }
 

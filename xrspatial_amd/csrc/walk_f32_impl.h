@@ -20,6 +20,7 @@ int launch(WalkGeom &g, const WalkOuts &o, hipStream_t s) {
     if (int rc = walk_grid(g, &grid)) return rc;
     hipLaunchKernelGGL((XRS_WALK_KERNEL<R, WANT_SUM, WANT_MM, F64>), dim3((unsigned)grid), dim3(256), 0, s, g, o);
     XRS_LAUNCH_CHECK();
+    route_note(XRS_STR(XRS_WALK_ENTRY), R);
     return 0;
 }
 

@@ -20,6 +20,7 @@ int launch64(WalkGeom &g, const WalkOuts &o, hipStream_t s) {
     else
         hipLaunchKernelGGL((XRS_WALK_KERNEL<R, false>), dim3((unsigned)grid), dim3(256), 0, s, g, o);
     XRS_LAUNCH_CHECK();
+    route_note(XRS_STR(XRS_WALK_ENTRY), R);
     return 0;
 }
 

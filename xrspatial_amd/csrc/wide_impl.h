@@ -899,6 +899,7 @@ int launch_wide(WideArgs &a, const WindowCall &c) {
                 if (int rc = launch_wide_rescue<R, Shape, WIDE_SUM>(a, tiles_y, s)) return rc;
         }
     }
+    route_note(XRS_STR(XRS_WIDE_ENTRY), R, Shape::hwi(R, 0), C::TW, 4 * C::TW, a.tile_rows, a.groups_x, tiles_y);
     return 0;
 }
 
@@ -923,6 +924,11 @@ int launch_wide_conv(WideArgs &a, const WindowCall &c) {
     if (grid > 0x7fffffffL) return fail("convolve_2d: raster too large for one launch");
     hipLaunchKernelGGL((focal_wide_kernel<R, Shape, WIDE_CONV>), dim3((unsigned)grid), dim3(256), 0, s, a);
     XRS_LAUNCH_CHECK();
+#ifdef XRS_WIDE_CONV_ENTRY
+    route_note(XRS_STR(XRS_WIDE_CONV_ENTRY), R, Shape::hwi(R, 0), C::TW, 4 * C::TW, a.tile_rows, a.groups_x, tiles_y);
+#else                                                          // (the annulus units: one entry for the mean and the convolution)
+    route_note(XRS_STR(XRS_WIDE_ENTRY), R, Shape::hwi(R, 0), C::TW, 4 * C::TW, a.tile_rows, a.groups_x, tiles_y);
+#endif
     return 0;
 }
 

@@ -25,6 +25,35 @@ inline int fail(const char *fmt, ...) {
     return 1;
 }
 
+// Route witness (xrs_debug_window_route): which launch groups served the thread's last focal / convolve_2d window call, in
+// launch order, and the tiling the strip walkers chose.  A plain per-thread record: cleared at the top of the three ABI
+// entries, written by the host launch functions once their kernels are enqueued.  Host code only.
+struct RouteItem {
+    const char *name;             // static text: a walker entry's name, or a branch tag of kxk.hip
+    int R, RI;                    // radius and inner radius; -1 = none
+    int wave_cols, wg_cols;       // columns of a wave tile and of a workgroup; 0 = the launch reports no geometry
+    int tile_rows;
+    long wgs_x, wgs_y;            // workgroups across and down
+};
+struct Route {
+    int n;
+    RouteItem item[8];
+};
+inline Route &route() {
+    static thread_local Route r = {};
+    return r;
+}
+inline void route_clear() { route().n = 0; }
+inline void route_note(const char *name, int R = -1, int RI = -1, int wave_cols = 0, int wg_cols = 0, int tile_rows = 0,
+                       long wgs_x = 0, long wgs_y = 0) {
+    Route &r = route();
+    if (r.n >= 8) return;
+    if (!strncmp(name, "try_launch_", 11)) name += 11;
+    r.item[r.n++] = RouteItem{name, R, RI, wave_cols, wg_cols, tile_rows, wgs_x, wgs_y};
+}
+#define XRS_STR_(x) #x
+#define XRS_STR(x) XRS_STR_(x)
+
 #define XRS_HIP(call)                                                                  \
     do {                                                                               \
         hipError_t e_ = (call);                                                        \
