@@ -658,6 +658,21 @@ int xrs_jenks_matrices_f32(const float *sorted_dev, int64_t n, int k, float *low
 int xrs_gather_elems(const void *in_dev, int elem_size, int64_t n, const uint32_t *idx_dev, int64_t n_idx, void *out_dev,
                      void *stream);
 
+/* bump (xrspatial/bump.py:12-28 `_finish_bump`): out_dev (height x width float64, row-major; zeroed by the call) after the
+ * reference's serial loop over `count` bumps -- locs_dev: count (x, y) uint16 pairs, heights_dev: count float64 -- bit for bit: bump
+ * i adds its height to its centre, then out[centre] * (d2 / spread^2) to every cell of its clipped footprint (upper bounds
+ * exclusive, the centre included with weight 0), every cell's sum taken in bump order, product and add rounded separately.
+ * spread <= 0 runs the centre adds only.  Events (cell, bump) are sorted by radix sort and folded in passes that never wait
+ * (DESIGN.md 6k); bumps are taken in index-order chunks whose events fit `max_events` (a capacity above count * footprint is cut
+ * to that).  Refused before any device work: null pointers, count < 0, width or height < 1, more than 2^31 cells, spread > 2^26, a
+ * capacity below one bump's footprint, a workspace below xrs_bump_workspace_bytes (0 for arguments the call refuses).  A location
+ * outside the raster is found on the device and reported; nothing is written for it.
+ * status (host, 8 int64, may be null): chunks, events, passes, touched cells summed over chunks, then the nanoseconds spent
+ * expanding (count, scan, emit), sorting (sort, segment heads) and folding. */
+size_t xrs_bump_workspace_bytes(int64_t count, int64_t width, int64_t height, int64_t spread, int64_t max_events);
+int xrs_bump_f64(const uint16_t *locs_dev, const double *heights_dev, int64_t count, int64_t width, int64_t height, int64_t spread,
+                 double *out_dev, void *work_dev, size_t work_bytes, int64_t max_events, int64_t *status, void *stream);
+
 /* multispectral.true_color (xrspatial/multispectral.py:1334-1495).
  *   xrs_nan_minmax_f32: minmax_dev[0..1] = np.nanmin / np.nanmax of a float32 plane (NaN, NaN if it holds no number);
  *   xrs_true_color_u8:  rgba[i] = { stretch(red), stretch(green), stretch(blue), alpha } with

@@ -4,7 +4,7 @@ Drop-in for the `xrspatial.*` functions on that path (same names, signatures, Da
 in/out): slope, aspect, hillshade, curvature, focal.mean / apply / focal_stats,
 convolution.convolve_2d / convolution_2d, multispectral ndvi / evi / savi (+ nbr, nbr2, ndmi),
 zonal.stats, zonal.regions, classify (binary, reclassify, equal_interval, quantile, percentiles, box_plot, std_mean,
-head_tail_breaks, maximum_breaks), natural_breaks, perlin, generate_terrain, viewshed, proximity / allocation / direction, a_star_search, local (cell_stats, combine, the frequencies, positions, rank, popularity),
+head_tail_breaks, maximum_breaks), natural_breaks, perlin, generate_terrain, bump, viewshed, proximity / allocation / direction, a_star_search, local (cell_stats, combine, the frequencies, positions, rank, popularity),
 experimental.polygonize.  Python host code calling hand-written HIP kernels through the C ABI of
 libxrs_hip.so (include/xrs_hip.h); no PyTorch, CuPy, Numba or Triton involved.
 
@@ -19,6 +19,7 @@ from .device import DeviceArray, empty_cache, synchronize  # noqa: F401
 from .utils import has_hip  # noqa: F401
 
 from .aspect import aspect  # noqa: F401
+from .bump import bump  # noqa: F401
 from .classify import (binary, box_plot, equal_interval, head_tail_breaks, maximum_breaks, percentiles,  # noqa: F401
                        quantile, reclassify, std_mean)
 from .curvature import curvature  # noqa: F401
