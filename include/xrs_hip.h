@@ -534,6 +534,32 @@ int xrs_hillshade_shadow_probe_f64(const double *data_dev, int64_t rows, int64_t
                                    double sun_x, double sun_y, double sun_z, int block, void *work_dev, float *out_dev,
                                    uint64_t *counts4_dev, void *stream);
 
+/* viewshed(method='mesh') (xrspatial/gpu_rtx/viewshed.py `_viewshed_rt` and gpu_rtx/mesh_utils.py `create_triangulation`, which
+ * trace one ray per cell through OptiX from the cell's surface point on the raster's triangle mesh to the observer): replaced by
+ * one bounded ray walk per cell over the same mesh, the result stated as a rule in DESIGN.md §6l and evaluated in float64.
+ * data_dev: rows x cols C-contiguous, at least 2 x 2, every cell finite (the caller checks).  scale, zmin, zmax: as for
+ * xrs_hillshade_shadow_*.  view_row / view_col: the observer's cell.  observer_elev / target_elev: heights in the raster's own
+ * units (scaled for the rays here, unscaled for the angles); ew_res / ns_res: the cell sizes that enter the angles only.
+ * out_dev (float32): 180 at the viewpoint, -1 where the cell's sight line hits the mesh, else the vertical angle in degrees.
+ * Two launches on the stream: the float32 vertex heights and a table of block maxima into work_dev
+ * (xrs_viewshed_mesh_workspace_bytes(rows, cols) bytes, caller-owned; the layout of xrs_hillshade_shadow_workspace_bytes),
+ * then the walk.  The probe entry points are for measuring (tools/viewshed_mesh_bench.py): the same walk with the block level
+ * over `block` x `block` cells (8, 16, 32; 0 = none; the entry points above use 32) and, where counts4_dev is not null, the
+ * { sum, max } of cells visited and { sum, max } of blocks tested per ray added into its four zeroed uint64. */
+size_t xrs_viewshed_mesh_workspace_bytes(int64_t rows, int64_t cols);
+int xrs_viewshed_mesh_f32(const float *data_dev, int64_t rows, int64_t cols, double scale, double zmin, double zmax, int64_t view_row,
+                          int64_t view_col, double observer_elev, double target_elev, double ew_res, double ns_res, void *work_dev,
+                          float *out_dev, void *stream);
+int xrs_viewshed_mesh_f64(const double *data_dev, int64_t rows, int64_t cols, double scale, double zmin, double zmax, int64_t view_row,
+                          int64_t view_col, double observer_elev, double target_elev, double ew_res, double ns_res, void *work_dev,
+                          float *out_dev, void *stream);
+int xrs_viewshed_mesh_probe_f32(const float *data_dev, int64_t rows, int64_t cols, double scale, double zmin, double zmax,
+                                int64_t view_row, int64_t view_col, double observer_elev, double target_elev, double ew_res,
+                                double ns_res, int block, void *work_dev, float *out_dev, uint64_t *counts4_dev, void *stream);
+int xrs_viewshed_mesh_probe_f64(const double *data_dev, int64_t rows, int64_t cols, double scale, double zmin, double zmax,
+                                int64_t view_row, int64_t view_col, double observer_elev, double target_elev, double ew_res,
+                                double ns_res, int block, void *work_dev, float *out_dev, uint64_t *counts4_dev, void *stream);
+
 /* proximity / allocation / direction (xrspatial/proximity.py `_process`): for every cell of a rows x cols C-contiguous raster
  * (`dtype`: XRS_DT_*) the exact nearest target, with the reference's float64 distance arithmetic rounded to float32, the
  * sweep's order among equidistant targets and its max_distance cut.

@@ -4,7 +4,7 @@ Drop-in for the `xrspatial.*` functions on that path (same names, signatures, Da
 in/out): slope, aspect, hillshade, curvature, focal.mean / apply / focal_stats,
 convolution.convolve_2d / convolution_2d, multispectral ndvi / evi / savi (+ nbr, nbr2, ndmi),
 zonal.stats, zonal.regions, classify (binary, reclassify, equal_interval, quantile, percentiles, box_plot, std_mean,
-head_tail_breaks, maximum_breaks), natural_breaks, perlin, generate_terrain, bump, viewshed, proximity / allocation / direction, a_star_search, local (cell_stats, combine, the frequencies, positions, rank, popularity),
+head_tail_breaks, maximum_breaks), natural_breaks, perlin, generate_terrain, bump, viewshed (the sweep and the ray-traced mesh variant), proximity / allocation / direction, a_star_search, local (cell_stats, combine, the frequencies, positions, rank, popularity),
 experimental.polygonize.  Python host code calling hand-written HIP kernels through the C ABI of
 libxrs_hip.so (include/xrs_hip.h); no PyTorch, CuPy, Numba or Triton involved.
 
@@ -36,7 +36,7 @@ from .proximity import (allocation, direction, euclidean_distance, great_circle_
                         proximity)
 from .slope import slope  # noqa: F401
 from .terrain import generate_terrain  # noqa: F401
-from .viewshed import viewshed  # noqa: F401
+from .viewshed import viewshed, viewshed_mesh  # noqa: F401
 from .zonal import crosstab as zonal_crosstab  # noqa: F401
 from .zonal import regions  # noqa: F401
 from .zonal import stats as zonal_stats  # noqa: F401

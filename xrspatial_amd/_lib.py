@@ -185,6 +185,15 @@ _PROTOTYPES = {
                                        c_void_p, c_void_p, c_void_p, c_void_p],
     "xrs_hillshade_shadow_probe_f64": [c_void_p, c_int64, c_int64, c_double, c_double, c_double, c_double, c_double, c_double, c_int,
                                        c_void_p, c_void_p, c_void_p, c_void_p],
+    "xrs_viewshed_mesh_workspace_bytes": [c_int64, c_int64],
+    "xrs_viewshed_mesh_f32": [c_void_p, c_int64, c_int64, c_double, c_double, c_double, c_int64, c_int64, c_double, c_double, c_double,
+                              c_double, c_void_p, c_void_p, c_void_p],
+    "xrs_viewshed_mesh_f64": [c_void_p, c_int64, c_int64, c_double, c_double, c_double, c_int64, c_int64, c_double, c_double, c_double,
+                              c_double, c_void_p, c_void_p, c_void_p],
+    "xrs_viewshed_mesh_probe_f32": [c_void_p, c_int64, c_int64, c_double, c_double, c_double, c_int64, c_int64, c_double, c_double,
+                                    c_double, c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    "xrs_viewshed_mesh_probe_f64": [c_void_p, c_int64, c_int64, c_double, c_double, c_double, c_int64, c_int64, c_double, c_double,
+                                    c_double, c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "xrs_proximity_workspace_bytes": [c_int64, c_int64],
     "xrs_proximity": [c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_int,
                       c_int, c_void_p, c_void_p, c_void_p],
@@ -230,7 +239,8 @@ _RESTYPES = {"xrs_kxk_workspace_bytes": c_size_t, "xrs_focal_workspace_bytes": c
              "xrs_proximity_workspace_bytes": c_size_t, "xrs_local_combine_workspace_bytes": c_size_t,
              "xrs_astar_workspace_bytes": c_size_t, "xrs_polygonize_workspace_bytes": c_size_t,
              "xrs_polygonize_rings_workspace_bytes": c_size_t, "xrs_hillshade_shadow_workspace_bytes": c_size_t,
-             "xrs_jenks_workspace_bytes": c_size_t, "xrs_bump_workspace_bytes": c_size_t}
+             "xrs_jenks_workspace_bytes": c_size_t, "xrs_bump_workspace_bytes": c_size_t,
+             "xrs_viewshed_mesh_workspace_bytes": c_size_t}
 
 EXPORTED = tuple(_PROTOTYPES)
 

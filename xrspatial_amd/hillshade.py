@@ -67,16 +67,38 @@ def sun_vector(azimuth, angle_altitude):
     return math.sin(az) * math.cos(alt), -math.cos(az) * math.cos(alt), math.sin(alt)
 
 
-def _height_scale(count, cells, zmin, zmax, rows, cols):
+def _height_scale(count, cells, zmin, zmax, rows, cols, what="hillshade(shadows=True)"):
     """rule 6's refusals and rule 2's scale from { count, min, max } of the finite cells"""
     if int(count) != cells:
-        raise ValueError(f"hillshade(shadows=True): the raster holds {cells - int(count)} non-finite cells")
+        raise ValueError(f"{what}: the raster holds {cells - int(count)} non-finite cells")
     if not zmax > 0:
-        raise ValueError(f"hillshade(shadows=True): the raster's maximum must be positive, got {zmax}")
+        raise ValueError(f"{what}: the raster's maximum must be positive, got {zmax}")
     scale = float(max(rows, cols)) / zmax                    # mesh_utils.py:17-19
     if not (math.isfinite(scale) and scale > 0):
-        raise ValueError(f"hillshade(shadows=True): the raster's maximum {zmax} gives no usable height scale")
+        raise ValueError(f"{what}: the raster's maximum {zmax} gives no usable height scale")
     return scale
+
+
+def mesh_source(data, stream, what="hillshade(shadows=True)"):
+    """(resident float32 / float64 raster, scale, min, max) for the mesh of rule 2, with rule 6's refusals; shared with
+    viewshed(method='mesh').  A host raster is checked where it lies, before any device work; a resident one by one reduction."""
+    rows, cols = data.shape
+    if isinstance(data, np.ndarray):
+        if np.dtype(data.dtype) not in _SUFFIX:              # integers, bool, float16: float64, as viewshed reads them
+            data = data.astype(np.float64)
+        count = int(np.isfinite(data).sum())
+        zmin, zmax = (float(data.min()), float(data.max())) if count == data.size else (math.nan, math.nan)
+        scale = _height_scale(count, data.size, zmin, zmax, rows, cols, what)
+        _lib.require_device()
+        return DeviceArray.from_numpy(np.ascontiguousarray(data), stream=stream), scale, zmin, zmax
+    _lib.require_device()
+    src = data if np.dtype(data.dtype) in _SUFFIX else DeviceArray.from_numpy(data.get(stream).astype(np.float64), stream=stream)
+    suffix = _SUFFIX[np.dtype(src.dtype)]
+    stats = DeviceArray((4,), np.float64)                    # { count, min, max, sum } of the finite cells, one pass
+    work = DeviceArray((int(_lib.load().xrs_classify_workspace_bytes(1, int(suffix == "f64"))),), np.uint8)
+    _lib.call("xrs_classify_finite_stats_" + suffix, src.ptr, rows * cols, work.ptr, stats.ptr, stream)
+    count, zmin, zmax, _ = (float(v) for v in stats.get(stream))
+    return src, _height_scale(count, rows * cols, zmin, zmax, rows, cols, what), zmin, zmax
 
 
 def _run_shadows(data, azimuth, angle_altitude, shadows=1):
@@ -87,23 +109,7 @@ def _run_shadows(data, azimuth, angle_altitude, shadows=1):
     like_numpy = isinstance(data, np.ndarray)
     rows, cols = data.shape
     stream = get_stream()
-    if like_numpy:                                           # a host raster is checked where it lies, before any device work
-        if np.dtype(data.dtype) not in _SUFFIX:              # integers, bool, float16: float64, as viewshed reads them
-            data = data.astype(np.float64)
-        count = int(np.isfinite(data).sum())
-        zmin, zmax = (float(data.min()), float(data.max())) if count == data.size else (math.nan, math.nan)
-        scale = _height_scale(count, data.size, zmin, zmax, rows, cols)
-        _lib.require_device()
-        src = DeviceArray.from_numpy(np.ascontiguousarray(data), stream=stream)
-    else:
-        _lib.require_device()
-        src = data if np.dtype(data.dtype) in _SUFFIX else DeviceArray.from_numpy(data.get(stream).astype(np.float64), stream=stream)
-        suffix = _SUFFIX[np.dtype(src.dtype)]
-        stats = DeviceArray((4,), np.float64)                # { count, min, max, sum } of the finite cells, one pass
-        work = DeviceArray((int(_lib.load().xrs_classify_workspace_bytes(1, int(suffix == "f64"))),), np.uint8)
-        _lib.call("xrs_classify_finite_stats_" + suffix, src.ptr, rows * cols, work.ptr, stats.ptr, stream)
-        count, zmin, zmax, _ = (float(v) for v in stats.get(stream))
-        scale = _height_scale(count, rows * cols, zmin, zmax, rows, cols)
+    src, scale, zmin, zmax = mesh_source(data, stream)
     out = DeviceArray((rows, cols), np.float32)
     work = DeviceArray((int(_lib.load().xrs_hillshade_shadow_workspace_bytes(rows, cols)),), np.uint8)
     _lib.call("xrs_hillshade_shadow_" + _SUFFIX[np.dtype(src.dtype)], src.ptr, rows, cols, scale, zmin, zmax, sun[0], sun[1], sun[2],
