@@ -146,6 +146,16 @@ int xrs_raster_pass_edges_f32(const float *in_dev, float *slope_dev, float *aspe
                               int kcols, void *work_dev, int64_t rows, int64_t cols, int64_t ld_in, int64_t ld_out,
                               double cellsize_x, double cellsize_y, double azimuth, double angle_altitude,
                               int halo_top, int halo_bot, int64_t edge_rows, void *stream);
+/* For tests: what served the calling thread's LAST xrs_raster_pass_f32 / xrs_raster_pass_edges_f32 call, as text, items
+ * joined by ';' in the order they were enqueued (a record of its own: xrs_debug_window_route is not touched).  A fused launch
+ * is  pass(ops=<set>,K=<3|5>,nt=<0|1>,cmask=<0|1>,tiles=<across>x<down>,seg=<first segment's tile rows>+<tile rows skipped>)
+ * with <set> the INSTANTIATED product set in the letters S, A, C, H ("-": the focal mean alone) -- slope alone reports SH --,
+ * nt the non-temporal store variant, cmask a compile-time mask, and tiles the launched workgroups (256 columns x 16 rows).
+ * The fall-backs are  terrain_fused(ops=<set>)  for the products the fused kernel leaves to xrs_terrain_fused_f32,
+ * focal_stats(K=<rows>x<cols>)  for a focal mean handed to xrs_focal_stats_f32, and  edges_split(rows=<edge_rows>)  in front
+ * of the items of the two sub-range calls the edges entry makes where one launch cannot take both edges.  Empty after a call
+ * that launched nothing.  Returns the length of the text (as snprintf); at most buflen - 1 bytes and a NUL are written. */
+int xrs_debug_pass_route(char *buf, size_t buflen);
 
 /* Geodesic slope / aspect (method='geodesic'): WGS-84 ECEF -> local ENU plane fit per 3x3 window, float64
  * arithmetic, float32 out, NaN border, NaN if any of the nine elevations is NaN.  Replaces

@@ -16,6 +16,8 @@ from xrspatial_amd import classify as cl
 
 _live = {}      # address -> ctypes buffer (keeps "device" allocations alive)
 _route = [""]   # what xrs_debug_window_route answers: the last window call, served by the oracle
+_pass_route = [""]   # what xrs_debug_pass_route answers: the last raster pass, served by the oracle
+_PASS_CALLS = ("xrs_raster_pass_f32", "xrs_raster_pass_edges_f32")
 _WINDOW_CALLS = ("xrs_focal_stats_f32", "xrs_focal_stats_f32_ex", "xrs_convolve2d_f32")
 
 
@@ -52,9 +54,14 @@ def _kernel(ptr, kr, kc):
     return _arr(ptr, kr * kc, np.float64).reshape(kr, kc).copy()
 
 
+_pass_depth = [0]    # > 0 inside the edges entry's own sub-range calls: the witness keeps naming the entry the caller used
+
+
 def call(name, *a):
     if name in _WINDOW_CALLS:
         _route[0] = "oracle:" + name
+    if name in _PASS_CALLS and not _pass_depth[0]:
+        _pass_route[0] = "oracle:" + name
     if name == "xrs_malloc":
         buf = ctypes.create_string_buffer(max(int(a[1]), 16) + 64)
         addr = (ctypes.addressof(buf) + 63) // 64 * 64
@@ -122,11 +129,15 @@ def call(name, *a):
         if edge == 0:
             return 0
         at = lambda p, rws, ld: (_host_ptr(p) + rws * int(ld) * 4) if p else None
-        call("xrs_raster_pass_f32", i, o_s, o_a, o_c, o_h, o_f, k, kr, kc, w, edge, cols, ld_i, ld_o, cx, cy, az, alt, ht,
-             rows - edge, st)
-        off = rows - edge
-        call("xrs_raster_pass_f32", at(i, off, ld_i), at(o_s, off, ld_o), at(o_a, off, ld_o), at(o_c, off, ld_o),
-             at(o_h, off, ld_o), at(o_f, off, ld_o), k, kr, kc, w, edge, cols, ld_i, ld_o, cx, cy, az, alt, rows - edge, hb, st)
+        _pass_depth[0] += 1
+        try:
+            call("xrs_raster_pass_f32", i, o_s, o_a, o_c, o_h, o_f, k, kr, kc, w, edge, cols, ld_i, ld_o, cx, cy, az, alt, ht,
+                 rows - edge, st)
+            off = rows - edge
+            call("xrs_raster_pass_f32", at(i, off, ld_i), at(o_s, off, ld_o), at(o_a, off, ld_o), at(o_c, off, ld_o),
+                 at(o_h, off, ld_o), at(o_f, off, ld_o), k, kr, kc, w, edge, cols, ld_i, ld_o, cx, cy, az, alt, rows - edge, hb, st)
+        finally:
+            _pass_depth[0] -= 1
     elif name in ("xrs_focal_stats_f32", "xrs_focal_stats_f32_ex"):
         if name.endswith("_ex"):
             a = a[:11] + a[12:14] + a[15:]           # (workspace size, accuracy flags: the oracle is exact either way)
@@ -347,6 +358,12 @@ class _FakeLib:
     @staticmethod
     def xrs_debug_window_route(buf, buflen):
         text = _route[0].encode()
+        ctypes.memmove(buf, text[:max(int(buflen) - 1, 0)] + b"\0", min(len(text) + 1, int(buflen)))
+        return len(text)
+
+    @staticmethod
+    def xrs_debug_pass_route(buf, buflen):
+        text = _pass_route[0].encode()
         ctypes.memmove(buf, text[:max(int(buflen) - 1, 0)] + b"\0", min(len(text) + 1, int(buflen)))
         return len(text)
 

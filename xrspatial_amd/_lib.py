@@ -80,6 +80,7 @@ _PROTOTYPES = {
     "xrs_raster_pass_edges_f32": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                   c_void_p, c_int64, c_int64, c_int64, c_int64, c_double, c_double, c_double, c_double,
                                   c_int, c_int, c_int64, c_void_p],
+    "xrs_debug_pass_route": [c_void_p, c_size_t],
     "xrs_geodesic_workspace_bytes": [c_int64, c_int64],
     "xrs_geodesic_f32": [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int64, c_int64, c_int64,
                          c_int64, c_double, c_double, c_double, c_int, c_void_p, c_int, c_int, c_void_p],
@@ -278,6 +279,13 @@ def window_route() -> str:
     """Which kernels served this thread's last focal / convolve_2d window call (xrs_debug_window_route); for tests."""
     buf = ctypes.create_string_buffer(1024)
     load().xrs_debug_window_route(buf, 1024)
+    return buf.value.decode(errors="replace")
+
+
+def pass_route() -> str:
+    """What served this thread's last xrs_raster_pass_f32 / xrs_raster_pass_edges_f32 call (xrs_debug_pass_route); for tests."""
+    buf = ctypes.create_string_buffer(1024)
+    load().xrs_debug_pass_route(buf, 1024)
     return buf.value.decode(errors="replace")
 
 

@@ -12,7 +12,8 @@
 // one -- so the fused kernel reads each cell once (4 B) and writes 4 B per product: 12 B per cell for
 // hillshade + focal mean, 16 B for hillshade + slope + focal mean (the 65536^2 target pipeline, 24 B unfused).
 // Arithmetic is the stand-alone kernels' (terrain_cells.h, focal_mean_direct_kernel): results are
-// bit-identical to separate launches, which tests/test_gpu_parity.py asserts.
+// bit-identical to separate launches, which tests/test_gpu_parity.py asserts; tests/test_gpu_raster_pass_census.py holds every
+// instantiation and strip path to float64 models of its own and to the route witness below.
 //
 // Any width / pitch / base address (dword-aligned 16-byte accesses, ragged last lane).  Masks larger than 5x5 run as
 // the separate launches -- same results, no fusion.
@@ -24,6 +25,38 @@
 using namespace xrs;
 
 namespace {
+
+// Route witness (xrs_debug_pass_route): what served the thread's last xrs_raster_pass_f32 / xrs_raster_pass_edges_f32 call, items
+// joined by ';' in the order they were enqueued.  A per-thread record of its own -- NOT xrs_common.h's window route, which
+// xrs_focal_stats_f32 keeps for its callers and which that entry's own call into this file must leave alone.  Cleared at the top
+// of the two ABI entries, written by host code only.
+struct PassRoute {
+    size_t n;
+    char text[1024];
+};
+PassRoute &pass_route() {
+    static thread_local PassRoute r = {};
+    return r;
+}
+void pass_route_clear() {
+    pass_route().n = 0;
+    pass_route().text[0] = 0;
+}
+__attribute__((format(printf, 1, 2))) void pass_route_note(const char *fmt, ...) {
+    PassRoute &r = pass_route();
+    if (r.n + 2 >= sizeof(r.text)) return;
+    if (r.n) r.text[r.n++] = ';';
+    va_list ap;
+    va_start(ap, fmt);
+    const int m = vsnprintf(r.text + r.n, sizeof(r.text) - r.n, fmt, ap);
+    va_end(ap);
+    if (m > 0) r.n = r.n + (size_t)m < sizeof(r.text) ? r.n + (size_t)m : sizeof(r.text) - 1;
+}
+// a product set in the witness's words: the letters of slope, aspect, curvature, hillshade; "-" = none
+const char *ops_text(int ops) {
+    static const char *const names[16] = {"-", "S", "A", "SA", "C", "SC", "AC", "SAC", "H", "SH", "AH", "SAH", "CH", "SCH", "ACH", "SACH"};
+    return names[ops & 15];
+}
 
 struct PassArgs {
     const float *in;
@@ -81,8 +114,11 @@ __device__ __forceinline__ void pass_body(const PassArgs &a, long x_tile, long y
     const unsigned rows_hit = strip_probe_rows(v);
 
     // ---- terrain products from the 3x3 centre of the registers (first: they need no accumulators)
-    auto terrain = [&](auto finite) {
+    // (returns, wave-uniform: the FINITE copy met a gradient whose square overflows -- hillshade_cell -- and its hillshade rows
+    //  are not valid)
+    auto terrain = [&](auto finite) -> bool {
         constexpr bool FINITE = decltype(finite)::value;
+        float tmax = 0.0f;
         const long y_lo = -(long)a.halo_top, y_hi = a.rows + a.halo_bot;
         const float qnan = nan_f32();
         // (slope / aspect: Horn sums cell by cell here -- sharing the differences along the strip (terrain.hip),
@@ -110,7 +146,7 @@ __device__ __forceinline__ void pass_body(const PassArgs &a, long x_tile, long y
                 if ((OPS & OP_ASPECT) && a.out[1]) o_aspect[o] = border ? qnan : aspect_from_horn(hs[o]);
                 if ((OPS & OP_CURV) && a.out[2]) o_curv[o] = border ? qnan : curvature_cell(q, a.curv_scale);
                 if ((OPS & OP_HILL) && a.out[3])
-                    o_hill[o] = border ? qnan : hillshade_cell<FINITE>(q, a.sin_alt, a.cos_alt, a.cos_az, a.sin_az);
+                    o_hill[o] = border ? qnan : hillshade_cell<FINITE>(q, a.sin_alt, a.cos_alt, a.cos_az, a.sin_az, &tmax);
             }
             const long off = y * a.ld_out + x_tile;
             const int nown = INTERIOR ? 4 : (int)(a.cols - x0 < 4 ? a.cols - x0 : 4);
@@ -119,12 +155,19 @@ __device__ __forceinline__ void pass_body(const PassArgs &a, long x_tile, long y
             if ((OPS & OP_CURV) && a.out[2]) put4<NT>(a.out[2] + off + loff, o_curv, nown);
             if ((OPS & OP_HILL) && a.out[3]) put4<NT>(a.out[3] + off + loff, o_hill, nown);
         }
+        return FINITE && __any(tmax == __builtin_inff());
     };
-    // (two copies only where the clean one is shorter: hillshade on interior strips)
-    if (INTERIOR && (OPS & OP_HILL) && rows_hit == 0u)
-        terrain(std::true_type{});
-    else
-        terrain(std::false_type{});
+    // (two copies only where the clean one is shorter: hillshade on interior strips.  Finite cells can still have a gradient
+    //  whose square is not -- 3e38 next to -3e38, a lone 1e20 -- which the short copy cannot shade: it reports that, and the
+    //  strip's products are written again by the general copy.  ALL of them, slope / aspect / curvature with the values they
+    //  already have: limiting the second pass to hillshade would put a run-time test in front of every store of the general copy,
+    //  the one strips with nodata run.  The rewrite relies on store ordering within a wave: every cell is stored twice by the SAME
+    //  lane, to the SAME address, through the SAME put4<NT> -- one kind of store -- in program order, and the memory model keeps
+    //  two stores of one work-item to one address in that order.  A change that gives the two copies different store kinds
+    //  (non-temporal against plain, or another lane layout) would have to fence between them.)
+    bool general = !(INTERIOR && (OPS & OP_HILL) && rows_hit == 0u);
+    if (!general) general = terrain(std::true_type{});
+    if (general) terrain(std::false_type{});
 
     // ---- focal mean: strip.h's strip_focal_mean (float64 sums == numba nanmean over the window; one body for clean strips,
     // strips with nodata and strips on the raster's edge).  (Round 2 tried float32 sums of values shifted by the lane's
@@ -197,6 +240,7 @@ int launch_pass(PassArgs &a, hipStream_t s) {
     unsigned mask = 0;
     for (int ky = 0; ky < K; ++ky) mask |= a.mask_rows[ky] << (ky * K);
     constexpr unsigned BOX = (1u << (K * K)) - 1u;                                              // np.ones((k, k))
+    const bool cmask = (K == 5 && mask == CIRCLE5) || (K == 3 && mask == BOX);
     if (K == 5 && mask == CIRCLE5) {
         if (a.nt_stores)
             hipLaunchKernelGGL((raster_pass_kernel<OPS, K, K, RB, true, K == 5 ? CIRCLE5 : 0u>), dim3((unsigned)grid), dim3(256), 0, s, a);
@@ -212,13 +256,17 @@ int launch_pass(PassArgs &a, hipStream_t s) {
     else
         hipLaunchKernelGGL((raster_pass_kernel<OPS, K, K, RB, false>), dim3((unsigned)grid), dim3(256), 0, s, a);
     XRS_LAUNCH_CHECK();
+    // the instantiation that ran (OPS: not the requested set), its tiling (256 columns x 4 * RB rows a workgroup) and segments
+    pass_route_note("pass(ops=%s,K=%d,nt=%d,cmask=%d,tiles=%ldx%ld,seg=%ld+%ld)", ops_text(OPS), K, a.nt_stores ? 1 : 0, cmask ? 1 : 0,
+                    a.tiles_x, a.n_tiles / a.tiles_x, a.seg_tiles_y, a.seg_skip);
     return 0;
 }
 
 // Instantiated product sets.  The focal mean fuses well with every terrain product (measured on 16384^2:
 // hillshade+focal 0.57 ms vs 0.79 ms as two launches, hillshade+slope+focal 0.84 vs 1.19).  Round 1 left aspect to
-// terrain.hip (its library atan2 on top of float64 Horn sums made the fused kernel VALU-bound); with the float32 Horn
-// sums and the octant-folded arc tangent of terrain_cells.h it rides along (own instantiations for aspect alone and
+// terrain.hip (its library atan2 on top of float64 Horn sums made the fused kernel VALU-bound); with the differences-first
+// float64 Horn sums (10 operations a cell, no float64 multiply) and the octant-folded float32 arc tangent of terrain_cells.h it
+// rides along (own instantiations for aspect alone and
 // aspect + hillshade; any other set with aspect takes the all-four instantiation).
 constexpr int FUSABLE = OP_SLOPE | OP_ASPECT | OP_CURV | OP_HILL;
 
@@ -314,6 +362,7 @@ static int raster_pass(const float *in_dev, float *slope_dev, float *aspect_dev,
                                work_dev, rows, cols, ld_in, ld_out, cellsize_x, cellsize_y, azimuth, angle_altitude, halo_top,
                                halo_bot, -1, stream);
         // two calls: the rows between the edges are the halo of either (as many of them as a window can reach)
+        pass_route_note("edges_split(rows=%ld)", (long)edge_rows);
         const int64_t between = rows - 2 * edge_rows, off = rows - edge_rows;
         const int inner = (int)(between + edge_rows < 4096 ? between + edge_rows : 4096);
         auto at = [](float *p, int64_t o) { return p ? p + o : nullptr; };
@@ -334,13 +383,18 @@ static int raster_pass(const float *in_dev, float *slope_dev, float *aspect_dev,
                                              cellsize_x, cellsize_y, azimuth, angle_altitude, halo_top, halo_bot,
                                              stream);
         if (rc) return rc;
+        pass_route_note("terrain_fused(ops=%s)", ops_text(rest));
     }
     if (!fast) {
         if (!focal_mean_dev) return 0;
         float *stat_outs[XRS_NUM_STATS] = {nullptr};
         stat_outs[XRS_STAT_MEAN] = focal_mean_dev;
-        return xrs_focal_stats_f32(in_dev, stat_outs, 1u << XRS_STAT_MEAN, rows, cols, ld_in, ld_out, kernel, krows,
-                                   kcols, work_dev, halo_top, halo_bot, stream);
+        const PassRoute so_far = pass_route();                     // (that entry may come back through xrs_raster_pass_f32)
+        const int rc = xrs_focal_stats_f32(in_dev, stat_outs, 1u << XRS_STAT_MEAN, rows, cols, ld_in, ld_out, kernel, krows,
+                                           kcols, work_dev, halo_top, halo_bot, stream);
+        pass_route() = so_far;
+        if (rc == 0) pass_route_note("focal_stats(K=%dx%d)", krows, kcols);
+        return rc;
     }
 
     PassArgs a;
@@ -369,6 +423,7 @@ extern "C" int xrs_raster_pass_f32(const float *in_dev, float *slope_dev, float 
                                    int kcols, void *work_dev, int64_t rows, int64_t cols, int64_t ld_in,
                                    int64_t ld_out, double cellsize_x, double cellsize_y, double azimuth,
                                    double angle_altitude, int halo_top, int halo_bot, void *stream) {
+    pass_route_clear();
     return raster_pass(in_dev, slope_dev, aspect_dev, curvature_dev, hillshade_dev, focal_mean_dev, kernel, krows, kcols,
                        work_dev, rows, cols, ld_in, ld_out, cellsize_x, cellsize_y, azimuth, angle_altitude, halo_top,
                        halo_bot, -1, stream);
@@ -380,8 +435,21 @@ extern "C" int xrs_raster_pass_edges_f32(const float *in_dev, float *slope_dev, 
                                          int64_t ld_out, double cellsize_x, double cellsize_y, double azimuth,
                                          double angle_altitude, int halo_top, int halo_bot, int64_t edge_rows,
                                          void *stream) {
+    pass_route_clear();
     if (edge_rows < 0) return fail("xrs_raster_pass_edges_f32: edge_rows must not be negative");
     return raster_pass(in_dev, slope_dev, aspect_dev, curvature_dev, hillshade_dev, focal_mean_dev, kernel, krows, kcols,
                        work_dev, rows, cols, ld_in, ld_out, cellsize_x, cellsize_y, azimuth, angle_altitude, halo_top,
                        halo_bot, edge_rows, stream);
+}
+
+// What served this thread's last xrs_raster_pass_f32 / xrs_raster_pass_edges_f32 call (PassRoute above).  Returns the length of
+// the full text (as snprintf), at most buflen - 1 bytes of which are written.
+extern "C" int xrs_debug_pass_route(char *buf, size_t buflen) {
+    const PassRoute &r = pass_route();
+    if (buf && buflen) {
+        const size_t m = r.n < buflen - 1 ? r.n : buflen - 1;
+        memcpy(buf, r.text, m);
+        buf[m] = 0;
+    }
+    return (int)r.n;
 }

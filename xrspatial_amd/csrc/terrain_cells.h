@@ -138,9 +138,13 @@ __device__ __forceinline__ float aspect_from_horn(const Horn &g) {
     // Written as its own test on (fx, fy) -- less than 4.98e-17 rad west of north <=> 0 < fx < -4.98e-17 fy -- whose verdict
     // waits in scalar registers: nesting `r < 2.85e-15f` into the select below cost the fused aspect instantiations
     // 33 .. 58 VGPRs and their third wave per SIMD (tools/spill_scan.py: 149 -> 206 for aspect + 5x5 mean).
+    // A hair EAST of north the same rounding answers 0 up to 1.72e-16 rad (the double below the one nearest pi/2 lies 2.83e-16
+    // below pi/2; the midpoint of the two, 1.72e-16): 0, not the 1e-14 degrees and less the direction really is off -- such
+    // cells lie next to every huge cell of a DEM (tests/test_gpu_raster_pass_census.py found one beside a lone 1e20).
     const bool hair_west = fx > 0.0f && fx < fy * -4.98e-17f;
+    const bool hair_east = fx < 0.0f && fx > fy * 1.7225e-16f;
     r = fx > 0.0f ? 360.0f - r : r;
-    r = hair_west ? 0.0f : r;
+    r = (hair_west || hair_east) ? 0.0f : r;
     r = __builtin_isunordered(fx, fy) ? nan_f32() : r;       // (fmax / fmin skip a NaN operand)
     return (fx == 0.0f && fy == 0.0f) ? -1.0f : r;
 }
@@ -153,13 +157,16 @@ __device__ __forceinline__ float curvature_cell(const Nb &q, double scale) {
     return (float)((d + e) * scale);
 }
 
-// FINITE: the caller knows every cell of the neighbourhood is finite (a strip whose rows all passed strip.h's vote): no
-// test for infinite gradients -- two v_cmp_class, an exec-mask branch and its bookkeeping per cell, 8 of the 30 instructions
-// a cell took.  1 / sqrt: v_rsq_f32 itself (1 ulp; the argument is >= 1, so the library wrapper's scaling of denormal
-// arguments -- 5 more instructions per cell -- never acts and the result is the same bit for bit).
+// FINITE: the caller knows every cell of the neighbourhood is finite (a strip whose rows all passed strip.h's vote) AND checks
+// `tmax` afterwards: no test for overflowing gradients -- a v_cmp_class, an exec-mask branch and its bookkeeping per cell.
+// Finite cells do not make finite gradients: 3e38 - (-3e38) is inf, and the square of a gradient beyond 1.8e19 (a lone 1e20
+// cell, which the vote does not see) is inf as well.  Either way the radicand t below is +inf, so the FINITE form folds every
+// cell's t into `tmax` (one v_max_f32) and the caller, after one vote on tmax per strip, runs the strip again through the
+// general form (pass.hip).  1 / sqrt: v_rsq_f32 itself (1 ulp; the argument is >= 1, so the library wrapper's scaling of
+// denormal arguments -- 5 more instructions per cell -- never acts and the result is the same bit for bit).
 template <bool FINITE = false>
 __device__ __forceinline__ float hillshade_cell(const Nb &q, float sin_alt, float cos_alt,
-                                                float cos_az, float sin_az) {
+                                                float cos_az, float sin_az, float *tmax = nullptr) {
 #pragma clang fp contract(off)   // (the fused multiply-adds below are explicit)
     // hillshade.py:24-31 with the trigonometry folded away: for gx = d/drow, gy = d/dcol,
     //   sin(pi/2 - atan g) = 1/sqrt(1+g^2),  cos(pi/2 - atan g) = g/sqrt(1+g^2),
@@ -167,22 +174,32 @@ __device__ __forceinline__ float hillshade_cell(const Nb &q, float sin_alt, floa
     // => shaded = (sin_alt + cos_alt*(cosA*gy - sinA*gx)) / sqrt(1 + gx^2 + gy^2).
     const float gx = (q.s - q.n) * 0.5f;
     const float gy = (q.e - q.w) * 0.5f;
-    if (!FINITE && __builtin_expect(isinf(gx) || isinf(gy), 0)) {
-        // An infinite gradient (+-inf cell in the DEM): the folded form would give inf * 0.  The reference's
-        // chain (hillshade.py:25-31) then has slope = pi/2 - atan(inf) = 0 exactly in float32, i.e.
-        // sin(slope) = 0 and cos(slope) = 1, and aspect = atan2(-gx, gy) is a multiple of pi/4, so
-        //   shaded = cos_alt * cos(A - aspect) = cos_alt * (cosA * cos(aspect) + sinA * sin(aspect))
-        // with (cos, sin)(aspect) read off the signs -- no trigonometry (and no inlined sinf / cosf argument
-        // reduction in every instantiation of the strip kernels).
-        if (isnan(gx) || isnan(gy)) return nan_f32();
-        const float r = (isinf(gx) && isinf(gy)) ? 0.70710678f : 1.0f;
-        const float ca = isinf(gy) ? copysignf(r, gy) : 0.0f;
-        const float sa = isinf(gx) ? copysignf(r, -gx) : 0.0f;
+    const float t = fmaf(gx, gx, fmaf(gy, gy, 1.0f));        // >= 1, +inf, or NaN (a NaN gradient: the folded form carries it)
+    if (FINITE) *tmax = fmaxf(*tmax, t);
+    if (!FINITE && __builtin_expect(t == __builtin_inff(), 0)) {
+        // g^2 overflows float32: the folded form would give num * 0 (or inf * 0).  The reference's chain (hillshade.py:25-31)
+        // then has sqrt(gx^2 + gy^2) = inf in float32, slope = pi/2 - atan(inf) = 0 exactly, i.e. sin(slope) = 0 and
+        // cos(slope) = 1:  shaded = cos_alt * cos(A - aspect) = cos_alt * (cosA * cos(aspect) + sinA * sin(aspect)).
+        float ca, sa;
+        if (isinf(gx) || isinf(gy)) {
+            // an infinite gradient (+-inf cell in the DEM, or two finite cells whose difference overflows): aspect =
+            // atan2(-gx, gy) is a multiple of pi/4, (cos, sin)(aspect) read off the signs -- no trigonometry (and no
+            // inlined sinf / cosf argument reduction in every instantiation of the strip kernels)
+            const float r = (isinf(gx) && isinf(gy)) ? 0.70710678f : 1.0f;
+            ca = isinf(gy) ? copysignf(r, gy) : 0.0f;
+            sa = isinf(gx) ? copysignf(r, -gx) : 0.0f;
+        } else {
+            // a finite gradient beyond 1.8e19: (cos, sin)(aspect) = (gy, -gx) / g, from the gradient scaled into range
+            const float sx = gx * 0x1p-64f, sy = gy * 0x1p-64f;
+            const float r = __builtin_amdgcn_rsqf(fmaf(sx, sx, sy * sy));
+            ca = sy * r;
+            sa = -sx * r;
+        }
         const double shaded = (double)cos_alt * (double)fmaf(cos_az, ca, sin_az * sa);
         return (float)((shaded + 1.0) * 0.5);
     }
     const float num = fmaf(cos_alt, fmaf(cos_az, gy, -sin_az * gx), sin_alt);
-    const float shaded = num * __builtin_amdgcn_rsqf(fmaf(gx, gx, fmaf(gy, gy, 1.0f)));
+    const float shaded = num * __builtin_amdgcn_rsqf(t);
     return (shaded + 1.0f) * 0.5f;
 }
 
