@@ -709,6 +709,35 @@ size_t xrs_bump_workspace_bytes(int64_t count, int64_t width, int64_t height, in
 int xrs_bump_f64(const uint16_t *locs_dev, const double *heights_dev, int64_t count, int64_t width, int64_t height, int64_t spread,
                  double *out_dev, void *work_dev, size_t work_bytes, int64_t max_events, int64_t *status, void *stream);
 
+/* D8 hydrology (no reference counterpart; the rule: xrspatial_amd/hydrology.py).
+ *   xrs_flow_direction   out_dev (float32) = the ESRI code (E 1, SE 2, S 4, SW 8, W 16, NW 32, N 64, NE 128) of the neighbour
+ *              with the largest drop (float64(z) - float64(zk)) / dist, dist = cellsize_x (E, W), cellsize_y (N, S), diag (the
+ *              rest), one IEEE subtraction and one IEEE division; neighbours in the order above, a later one only when its
+ *              drop is strictly larger; 0 where no neighbour lies lower, NaN at NaN cells.  `dtype`: XRS_DT_F32 or XRS_DT_F64.
+ *              The cell sizes and `diag` (the caller's sqrt(cx^2 + cy^2)) are positive and finite.  One launch.
+ *   xrs_flow_accumulate  dir_dev: a float32 plane of such codes (NaN: the cell is outside the graph), at most
+ *              XRS_FLOW_MAX_CELLS cells.  acc_out_dev (float64, or NULL): the number of cells whose path reaches the cell, itself
+ *              included.  basin_out_dev (float64, or NULL): the linear index of the outlet the cell's path ends in.  Both NaN at
+ *              NaN cells.  A cell whose code is 0, or names a neighbour outside the raster or a NaN neighbour, is an outlet.
+ *              Pointer doubling: at most (rows * cols).bit_length() rounds, the live pointers counted by every round and read
+ *              by the host every two rounds (the call waits for the stream then).
+ *   work_dev   xrs_flow_workspace_bytes(rows, cols, want) bytes, caller-owned; `want`: XRS_FLOW_ACCUMULATION | XRS_FLOW_BASINS,
+ *              covering the products asked for (0 bytes for an empty raster, one beyond the cell limit or an empty `want`).
+ *   status_host HOST array of XRS_FLOW_STATUS_WORDS words: [0] rounds that had live pointers; [1] XRS_FLOW_INVALID_CODE (a
+ *              non-NaN value that is no code) | XRS_FLOW_CYCLE (a pointer still live after the bound: the raster holds a cycle)
+ *              -- with either bit set the call returns 0 and writes no product; [2], [3] nanoseconds of decode and finish;
+ *              [4 + k] live pointers anc_k; [40 + k] nanoseconds of round k.  The times only with XRS_FLOW_TIMED in `flags`
+ *              (a stream sync after every launch: tools/hydrology_bench.py). */
+enum { XRS_FLOW_ACCUMULATION = 1, XRS_FLOW_BASINS = 2 };
+enum { XRS_FLOW_INVALID_CODE = 1, XRS_FLOW_CYCLE = 2 };
+enum { XRS_FLOW_TIMED = 1, XRS_FLOW_MAX_ROUNDS = 32, XRS_FLOW_STATUS_WORDS = 80 };
+#define XRS_FLOW_MAX_CELLS 0xfffffffeull       /* 2^32 - 2: the all-ones word is the null pointer */
+int xrs_flow_direction(const void *data_dev, int dtype, int64_t rows, int64_t cols, double cellsize_x, double cellsize_y, double diag,
+                       float *out_dev, void *stream);
+size_t xrs_flow_workspace_bytes(int64_t rows, int64_t cols, int want);
+int xrs_flow_accumulate(const float *dir_dev, int64_t rows, int64_t cols, void *work_dev, double *acc_out_dev, double *basin_out_dev,
+                        int64_t *status_host, int flags, void *stream);
+
 /* multispectral.true_color (xrspatial/multispectral.py:1334-1495).
  *   xrs_nan_minmax_f32: minmax_dev[0..1] = np.nanmin / np.nanmax of a float32 plane (NaN, NaN if it holds no number);
  *   xrs_true_color_u8:  rgba[i] = { stretch(red), stretch(green), stretch(blue), alpha } with

@@ -222,6 +222,9 @@ _PROTOTYPES = {
     "xrs_bump_workspace_bytes": [c_int64, c_int64, c_int64, c_int64, c_int64],
     "xrs_bump_f64": [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_size_t, c_int64,
                      ctypes.POINTER(c_int64), c_void_p],
+    "xrs_flow_direction": [c_void_p, c_int, c_int64, c_int64, c_double, c_double, c_double, c_void_p, c_void_p],
+    "xrs_flow_workspace_bytes": [c_int64, c_int64, c_int],
+    "xrs_flow_accumulate": [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int64), c_int, c_void_p],
     "xrs_comm_unique_id": [c_void_p],
     "xrs_comm_init_rank": [ctypes.POINTER(c_void_p), c_void_p, c_int, c_int],
     "xrs_comm_destroy": [c_void_p],
@@ -241,7 +244,7 @@ _RESTYPES = {"xrs_kxk_workspace_bytes": c_size_t, "xrs_focal_workspace_bytes": c
              "xrs_astar_workspace_bytes": c_size_t, "xrs_polygonize_workspace_bytes": c_size_t,
              "xrs_polygonize_rings_workspace_bytes": c_size_t, "xrs_hillshade_shadow_workspace_bytes": c_size_t,
              "xrs_jenks_workspace_bytes": c_size_t, "xrs_bump_workspace_bytes": c_size_t,
-             "xrs_viewshed_mesh_workspace_bytes": c_size_t}
+             "xrs_viewshed_mesh_workspace_bytes": c_size_t, "xrs_flow_workspace_bytes": c_size_t}
 
 EXPORTED = tuple(_PROTOTYPES)
 
