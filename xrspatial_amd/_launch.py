@@ -16,6 +16,7 @@ import numpy as np
 from . import _lib
 from .device import _CAST_CODE, DeviceArray, host_empty, is_pinned, to_device_f32
 from .sharded import ShardedArray
+from .utils import is_dask
 
 # The stream every host-level call uses (None = HIP null stream).  bench.py swaps in its own.
 _stream = None
@@ -46,6 +47,73 @@ def finish(out: DeviceArray, like_numpy: bool):
     if like_numpy:
         return out.get(_stream)
     return out
+
+
+# ------------------------------------------------------------------ whole-raster calls
+# proximity, a_star_search, viewshed, hillshade(shadows=True), the flow graph, zonal.regions, polygonize, the local family and the
+# noise planes read cells far from the one they write: one call takes the whole raster, on one GPU.  What they share on the host:
+def refuse_split_backends(agg, what, sharded=None, dask=None, named=None, others=False):
+    """Return for NumPy- and DeviceArray-backed `agg`; NotImplementedError for the backends that hold a raster in pieces.
+
+    `sharded` / `dask`: the caller's own text where it is not `<what>() does not support ... DataArray` (`what` may be None where
+    both are given).  Any other backend is a TypeError naming the type of `named` (default: of `agg`, as `ArrayTypeFunctionMapping`
+    names it), unless `others` lets it through to the caller's own checks."""
+    data = agg.data
+    if isinstance(data, (np.ndarray, DeviceArray)):
+        return
+    if isinstance(data, ShardedArray):
+        raise NotImplementedError(sharded or f'{what}() does not support row-sharded (multi-GPU) DataArray')
+    if is_dask(data):
+        raise NotImplementedError(dask or f'{what}() does not support dask backed DataArray')
+    if not others:
+        raise TypeError("Unsupported Array Type: {}".format(type(agg if named is None else named)))
+
+
+def widened(data, stream, readable, widen):
+    """`data` as the kernel can read it: itself when its dtype is in `readable`, else a host copy cast to `widen` (a dtype, or a
+    callable dtype -> dtype that raises the caller's TypeError); a DeviceArray pays one round trip through host memory for it."""
+    dtype = np.dtype(data.dtype)
+    if dtype in readable:
+        return data
+    wider = widen if isinstance(widen, type) else widen(dtype)
+    return (data.get(stream) if isinstance(data, DeviceArray) else data).astype(wider)
+
+
+def resident(data, stream, readable=None, widen=None):
+    """(the raster in HBM, like_numpy): a DeviceArray stays where it is, a host raster goes up in its own dtype; with `readable`
+    after `widened`.  `like_numpy` says what the caller gave, whatever the staging did: it is `finish`'s and `settle`'s argument."""
+    like_numpy = not isinstance(data, DeviceArray)
+    if readable is not None:
+        data = widened(data, stream, readable, widen)
+    return (data if isinstance(data, DeviceArray) else DeviceArray.from_numpy(data, stream=stream)), like_numpy
+
+
+def workspace(name, *args, at_least=0):
+    """The uint8 scratch block `xrs_<name>_workspace_bytes(*args)` asks for (`at_least`: callers whose launch wants a block even
+    when the answer is 0)."""
+    return DeviceArray((max(_lib.workspace_bytes(name, *args), at_least),), np.uint8)
+
+
+def settle(stream, like_numpy=False):
+    """The trailing `xrs_stream_sync` of a whole-raster call, skipped where `finish(out, like_numpy)` follows with a download.
+
+    What a call must have waited for when it returns is what the HOST can see of it: memory the device or an asynchronous copy
+    writes into (status words, counters, a downloaded table), and host buffers a launch still reads (a kernel passed by pointer).
+    Every entry point that fills host words waits for them itself before it returns (xrs_astar, xrs_flow_accumulate,
+    xrs_regions_link, xrs_polygonize_*, xrs_local_combine, xrs_bump_f64), and `DeviceArray.get` / `from_numpy` sync their own copy.
+    A NumPy-backed call needs nothing more: `finish` downloads the result on the same stream and syncs, so everything launched
+    before it is done before the workspace and the staged copies are dropped.
+
+    The callers' comment is another reason: "the workspace goes back to the pool when this returns".  For that the pool has its
+    own guard.  `device._raw_free` records an event on the active stream (`get_stream()`) when a block is pooled, `_raw_alloc` waits
+    for that event before it hands the block to anybody, and a block the pool has no room for goes to `xrs_free` (hipFree, which waits for
+    the device).  So a block freed behind a launch ON THE ACTIVE STREAM cannot be reused before the launch is through, sync or no
+    sync; focal's `_window_workspace` already relies on it.  The sync still matters in two corners: a launch on a stream that is
+    not the active one (`flow_graph(..., stream=other)` from a tool), and a block pooled without a fence because the event
+    could not be created.  Given the fence the other trailing syncs look redundant; none has been removed, because nobody has
+    measured what they cost or run the suites without them."""
+    if not like_numpy:
+        _lib.call("xrs_stream_sync", stream)
 
 
 # ------------------------------------------------------------------ banded host pipeline

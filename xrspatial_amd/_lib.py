@@ -26,7 +26,7 @@ class XrsError(RuntimeError):
     """A libxrs_hip.so entry point returned non-zero."""
 
 
-# name -> argtypes (every function returns int unless listed in _RESTYPES)
+# name -> argtypes (every function returns int, except that a `*_workspace_bytes` returns size_t: load() goes by the name)
 _PROTOTYPES = {
     "xrs_version": [],
     "xrs_last_error": [ctypes.c_char_p, c_size_t],
@@ -236,16 +236,6 @@ _PROTOTYPES = {
     "xrs_allreduce_u8": [c_void_p, c_void_p, c_int64, c_int, c_void_p],
     "xrs_allreduce_u64": [c_void_p, c_void_p, c_int64, c_int, c_void_p],
 }
-_RESTYPES = {"xrs_kxk_workspace_bytes": c_size_t, "xrs_focal_workspace_bytes": c_size_t, "xrs_zonal_majority_workspace_bytes": c_size_t,
-             "xrs_zonal_mode_workspace_bytes": c_size_t,
-             "xrs_geodesic_workspace_bytes": c_size_t, "xrs_classify_workspace_bytes": c_size_t,
-             "xrs_regions_workspace_bytes": c_size_t, "xrs_viewshed_workspace_bytes": c_size_t,
-             "xrs_proximity_workspace_bytes": c_size_t, "xrs_local_combine_workspace_bytes": c_size_t,
-             "xrs_astar_workspace_bytes": c_size_t, "xrs_polygonize_workspace_bytes": c_size_t,
-             "xrs_polygonize_rings_workspace_bytes": c_size_t, "xrs_hillshade_shadow_workspace_bytes": c_size_t,
-             "xrs_jenks_workspace_bytes": c_size_t, "xrs_bump_workspace_bytes": c_size_t,
-             "xrs_viewshed_mesh_workspace_bytes": c_size_t, "xrs_flow_workspace_bytes": c_size_t}
-
 EXPORTED = tuple(_PROTOTYPES)
 
 _lib = None
@@ -267,9 +257,14 @@ def load():
             for name, argtypes in _PROTOTYPES.items():
                 fn = getattr(lib, name)
                 fn.argtypes = argtypes
-                fn.restype = _RESTYPES.get(name, c_int)
+                fn.restype = c_size_t if name.endswith("_workspace_bytes") else c_int
             _lib = lib
     return _lib
+
+
+def workspace_bytes(name: str, *args) -> int:
+    """What `xrs_<name>_workspace_bytes(*args)` answers: the bytes of device scratch the call of that name needs."""
+    return int(getattr(load(), f"xrs_{name}_workspace_bytes")(*args))
 
 
 def last_error() -> str:

@@ -63,9 +63,8 @@ def finish_bump(width, height, locs, heights, spread, device=False, *, max_event
     z = _heights_f64(heights, count)
     max_events = DEFAULT_MAX_EVENTS if max_events is None else operator.index(max_events)
     _lib.require_device()
-    lib = _lib.load()
     stream = get_stream()
-    nbytes = int(lib.xrs_bump_workspace_bytes(count, width, height, spread, max_events))
+    nbytes = _lib.workspace_bytes("bump", count, width, height, spread, max_events)
     out = DeviceArray((height, width), np.float64)
     # (a workspace of 0 bytes: the call refuses the arguments and says why)
     work = DeviceArray((max(nbytes, 256),), np.uint8)

@@ -17,7 +17,7 @@ import warnings
 import numpy as np
 
 from . import _lib
-from ._launch import finish, get_stream, percell_pipelined
+from ._launch import finish, get_stream, percell_pipelined, workspace
 from ._xr import DataArray
 from .dataset_support import supports_dataset
 from .device import DTYPE_CODE, DeviceArray
@@ -195,7 +195,7 @@ class _Stats:
         self.n = dev.size
         # reductions and the select need a fixed few hundred KiB (the workspace of a 1-cell call); the sort of
         # maximum_breaks a multiple of the raster, allocated when it runs
-        self.work = DeviceArray((_lib.load().xrs_classify_workspace_bytes(1, int(self.suffix == "f64")),), np.uint8)
+        self.work = workspace("classify", 1, int(self.suffix == "f64"))
         self.out = DeviceArray((4,), np.float64)
         self._moments = None
 
@@ -247,7 +247,7 @@ class _Stats:
             out = DeviceArray((self.n + 1,), np.float64)
         else:
             out = DeviceArray((2 + 4 * n_top + 1,), np.float64)
-        work = DeviceArray((_lib.load().xrs_classify_workspace_bytes(self.n, int(self.suffix == "f64")),), np.uint8)
+        work = workspace("classify", self.n, int(self.suffix == "f64"))
         _lib.call(f"xrs_classify_max_breaks_{self.suffix}", self.src.ptr, self.n, int(n_top), work.ptr, work.nbytes,
                   out.ptr, get_stream())
         if n_top < 0:

@@ -11,7 +11,7 @@ import re
 import numpy as np
 
 from . import _lib
-from ._launch import finish, get_stream, pipeline_ok, pipelined_rows, plane_args, sharded_f32
+from ._launch import finish, get_stream, pipeline_ok, pipelined_rows, plane_args, sharded_f32, workspace
 from ._xr import DataArray
 from .device import DeviceArray, to_device_f32
 from .sharded import ShardedArray
@@ -113,7 +113,7 @@ def _convolve_2d_hip(data, kernel):
     if pipeline_ok(data) and max(k.shape) // 2 < 128:
         # large numpy raster: row bands upload / compute / download concurrently
         cols = data.shape[1]
-        work = DeviceArray((max(int(_lib.load().xrs_kxk_workspace_bytes(k.shape[0], k.shape[1])), 16),), np.uint8)
+        work = workspace("kxk", k.shape[0], k.shape[1], at_least=16)
 
         def launch(in_ptr, out_ptrs, n_rows, ht, hb, stream):
             _lib.call("xrs_convolve2d_f32", in_ptr, out_ptrs[0], n_rows, cols, cols, cols, k.ctypes.data, k.shape[0],
@@ -123,7 +123,7 @@ def _convolve_2d_hip(data, kernel):
     src = to_device_f32(data)
     rows, cols, ld = plane_args(src)
     out = DeviceArray((rows, cols), np.float32)
-    work = DeviceArray((max(int(_lib.load().xrs_kxk_workspace_bytes(k.shape[0], k.shape[1])), 16),), np.uint8)
+    work = workspace("kxk", k.shape[0], k.shape[1], at_least=16)
     stream = get_stream()
     _lib.call("xrs_convolve2d_f32", src.ptr, out.ptr, rows, cols, ld, ld, k.ctypes.data, k.shape[0],
               k.shape[1], work.ptr, 0, 0, stream)
@@ -140,7 +140,7 @@ def _convolve_2d_sharded(data, kernel):
     ht, hb = src.halos(k.shape[0] // 2, stream)
     rows, cols = src.shape
     out = src.like(np.float32)
-    work = DeviceArray((max(int(_lib.load().xrs_kxk_workspace_bytes(k.shape[0], k.shape[1])), 16),), np.uint8)
+    work = workspace("kxk", k.shape[0], k.shape[1], at_least=16)
     _lib.call("xrs_convolve2d_f32", src.ptr, out.ptr, rows, cols, cols, cols, k.ctypes.data, k.shape[0],
               k.shape[1], work.ptr, ht, hb, stream)
     _lib.call("xrs_stream_sync", stream)      # `k` and `work` must outlive the launch

@@ -229,6 +229,9 @@ _CAST_CODE = {np.dtype(t): c for c, t in enumerate(
 DTYPE_CODE = dict(_CAST_CODE)
 DTYPE_CODE[np.dtype(np.float32)] = 9
 
+# the two dtypes of the kernels built once per float width, and the suffix of their entry points (`xrs_viewshed_f32`, ...)
+FLOAT_SUFFIX = {np.dtype(np.float32): "f32", np.dtype(np.float64): "f64"}
+
 
 def _cast_f32_on_device(src: "DeviceArray", stream=None, src_is_temporary=True) -> "DeviceArray":
     out = DeviceArray(src.shape, np.float32)

@@ -22,7 +22,7 @@ from typing import Optional
 import numpy as np
 
 from .. import _lib
-from .._launch import get_stream
+from .._launch import get_stream, resident, settle, workspace
 from .._xr import DataArray
 from ..device import DTYPE_CODE, DeviceArray
 
@@ -66,13 +66,10 @@ def flat(values, mask, connectivity_8, transform, stats=None):
                          "split your raster into smaller chunks.")
     mask_code = _mask_code(mask.dtype) if mask is not None else 0
     _lib.require_device()
-    lib = _lib.load()
     stream = get_stream()
-    dev = values if isinstance(values, DeviceArray) else DeviceArray.from_numpy(np.ascontiguousarray(values), stream=stream)
-    mdev = None
-    if mask is not None:
-        mdev = mask if isinstance(mask, DeviceArray) else DeviceArray.from_numpy(np.ascontiguousarray(mask), stream=stream)
-    work = DeviceArray((int(lib.xrs_polygonize_workspace_bytes(rows, cols)),), np.uint8)
+    dev, _ = resident(values, stream)
+    mdev = resident(mask, stream)[0] if mask is not None else None
+    work = workspace("polygonize", rows, cols)
     n_regions, n_states = ctypes.c_uint64(0), ctypes.c_uint64(0)
     _lib.call("xrs_polygonize_census", dev.ptr, DTYPE_CODE[dtype], mdev.ptr if mdev is not None else None, mask_code, rows, cols,
               8 if connectivity_8 else 4, work.ptr, ctypes.byref(n_regions), ctypes.byref(n_states), stream)
@@ -86,7 +83,7 @@ def flat(values, mask, connectivity_8, transform, stats=None):
     if n_states > MAX_STATES:
         raise ValueError(f"polygonize: {n_states} boundary states exceed the {MAX_STATES} this backend ranks; "
                          "split your raster into smaller chunks.")
-    ring_bytes = int(lib.xrs_polygonize_rings_workspace_bytes(n_states))
+    ring_bytes = _lib.workspace_bytes("polygonize_rings", n_states)
     # the ring workspace, then the points (at most one per state and one more per ring) and the offsets
     need = ring_bytes + (n_states + n_states // 4 + 1) * 16 + (n_states // 4 + 2) * 16 + n_regions * dtype.itemsize
     free = _free_bytes()
@@ -111,7 +108,7 @@ def flat(values, mask, connectivity_8, transform, stats=None):
     _lib.call("xrs_polygonize_scatter", dev.ptr, DTYPE_CODE[dtype], rows, cols, work.ptr, rings.ptr, n_states, n_regions, n_rings,
               tf, points.ptr, ring_offsets.ptr, polygon_offsets.ptr, column.ptr, stream)
     out = (column.get(stream), points.get(stream), ring_offsets.get(stream), polygon_offsets.get(stream))
-    _lib.call("xrs_stream_sync", stream)                 # the workspaces go back to the pool
+    settle(stream)                                       # the workspaces go back to the pool
     return out
 
 

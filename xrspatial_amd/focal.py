@@ -9,7 +9,7 @@ import os
 import numpy as np
 
 from . import _lib, fused
-from ._launch import finish, get_stream, pipeline_ok, pipelined_rows, plane_args, sharded_f32
+from ._launch import finish, get_stream, pipeline_ok, pipelined_rows, plane_args, sharded_f32, workspace
 from ._xr import DataArray
 from .convolution import _kernel_f64, custom_kernel
 from .dataset_support import supports_dataset
@@ -136,7 +136,7 @@ def _window_workspace(k, rows=0, cols=0):
     walked = k.shape[0] == k.shape[1] and 7 <= k.shape[0] <= 25 and k.shape[0] % 2 == 1
     if not (big or walked):
         return None
-    return DeviceArray((int(_lib.load().xrs_focal_workspace_bytes(int(rows), int(cols), k.shape[0], k.shape[1])),), np.uint8)
+    return workspace("focal", int(rows), int(cols), k.shape[0], k.shape[1])
 
 
 def _apply_sharded(data, kernel, stat):

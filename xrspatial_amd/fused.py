@@ -24,7 +24,7 @@ import threading
 import numpy as np
 
 from . import _lib
-from ._launch import get_stream, sharded_f32
+from ._launch import get_stream, sharded_f32, workspace
 from ._xr import DataArray
 from .device import DeviceArray, to_device_f32
 from .sharded import ShardedArray
@@ -141,8 +141,7 @@ class fuse:
             k = fm[1]['kernel'] if fm else None
             work = None
             if k is not None and max(k.shape) > 5:
-                nbytes = max(int(_lib.load().xrs_kxk_workspace_bytes(k.shape[0], k.shape[1])), 16)
-                work = DeviceArray((nbytes,), np.uint8)
+                work = workspace("kxk", k.shape[0], k.shape[1], at_least=16)
             # a row-sharded raster: the pass reads the neighbours' rows from the shard's halo (one exchange per raster)
             ht, hb = src.halos(max(1, k.shape[0] // 2 if k is not None else 1), stream) if sharded else (0, 0)
             ptr = lambda s: outs[s].ptr if s in outs else None          # noqa: E731

@@ -9,7 +9,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _lib
-from ._launch import finish, get_stream
+from ._launch import finish, get_stream, workspace
 from .device import DeviceArray
 
 WGS84_A2 = 6378137.0 * 6378137.0
@@ -90,10 +90,7 @@ def run_geodesic(data, lat, lon, is_2d, z_factor, aspect):
         raise ValueError("1-D lat/lon coordinates must match the raster's last two dims")
     lat_dev, lon_dev = DeviceArray.from_numpy(lat), DeviceArray.from_numpy(lon)
     out = DeviceArray((rows, cols), np.float32)
-    work = None
-    if not is_2d:
-        nbytes = int(_lib.load().xrs_geodesic_workspace_bytes(rows, cols))
-        work = DeviceArray((nbytes,), np.uint8)
+    work = None if is_2d else workspace("geodesic", rows, cols)
     _lib.call("xrs_geodesic_f32", src.ptr, int(src.dtype == np.float64), lat_dev.ptr, lon_dev.ptr, int(is_2d),
               out.ptr, rows, cols, cols, cols, cols, WGS84_A2, WGS84_B2, float(z_factor), int(aspect),
               work.ptr if work is not None else None, 0, 0, get_stream())

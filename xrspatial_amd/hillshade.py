@@ -30,10 +30,10 @@ from typing import Optional
 import numpy as np
 
 from . import _lib, fused
-from ._launch import finish, get_stream, stencil
+from ._launch import finish, get_stream, refuse_split_backends, resident, settle, stencil, widened, workspace
 from ._xr import DataArray
 from .dataset_support import supports_dataset
-from .device import DeviceArray
+from .device import FLOAT_SUFFIX, DeviceArray
 from .sharded import ShardedArray
 from .utils import dask_overlap, is_dask
 
@@ -58,9 +58,6 @@ def _hill(data, out_dtype, azimuth, angle_altitude):
 
 
 # ------------------------------------------------------------------ shadows=True (module docstring)
-_SUFFIX = {np.dtype(np.float32): "f32", np.dtype(np.float64): "f64"}
-
-
 def sun_vector(azimuth, angle_altitude):
     """rule 1: the unit vector towards the sun (gpu_rtx/hillshade.py:133-143 `_get_sun_dir`, without the rotations)"""
     az, alt = math.radians(float(azimuth)), math.radians(float(angle_altitude))
@@ -84,18 +81,17 @@ def mesh_source(data, stream, what="hillshade(shadows=True)"):
     viewshed(method='mesh').  A host raster is checked where it lies, before any device work; a resident one by one reduction."""
     rows, cols = data.shape
     if isinstance(data, np.ndarray):
-        if np.dtype(data.dtype) not in _SUFFIX:              # integers, bool, float16: float64, as viewshed reads them
-            data = data.astype(np.float64)
+        data = widened(data, stream, FLOAT_SUFFIX, np.float64)         # integers, bool, float16: float64, as viewshed reads them
         count = int(np.isfinite(data).sum())
         zmin, zmax = (float(data.min()), float(data.max())) if count == data.size else (math.nan, math.nan)
         scale = _height_scale(count, data.size, zmin, zmax, rows, cols, what)
         _lib.require_device()
-        return DeviceArray.from_numpy(np.ascontiguousarray(data), stream=stream), scale, zmin, zmax
+        return resident(data, stream)[0], scale, zmin, zmax
     _lib.require_device()
-    src = data if np.dtype(data.dtype) in _SUFFIX else DeviceArray.from_numpy(data.get(stream).astype(np.float64), stream=stream)
-    suffix = _SUFFIX[np.dtype(src.dtype)]
+    src, _ = resident(data, stream, FLOAT_SUFFIX, np.float64)
+    suffix = FLOAT_SUFFIX[src.dtype]
     stats = DeviceArray((4,), np.float64)                    # { count, min, max, sum } of the finite cells, one pass
-    work = DeviceArray((int(_lib.load().xrs_classify_workspace_bytes(1, int(suffix == "f64"))),), np.uint8)
+    work = workspace("classify", 1, int(suffix == "f64"))
     _lib.call("xrs_classify_finite_stats_" + suffix, src.ptr, rows * cols, work.ptr, stats.ptr, stream)
     count, zmin, zmax, _ = (float(v) for v in stats.get(stream))
     return src, _height_scale(count, rows * cols, zmin, zmax, rows, cols, what), zmin, zmax
@@ -111,11 +107,10 @@ def _run_shadows(data, azimuth, angle_altitude, shadows=1):
     stream = get_stream()
     src, scale, zmin, zmax = mesh_source(data, stream)
     out = DeviceArray((rows, cols), np.float32)
-    work = DeviceArray((int(_lib.load().xrs_hillshade_shadow_workspace_bytes(rows, cols)),), np.uint8)
-    _lib.call("xrs_hillshade_shadow_" + _SUFFIX[np.dtype(src.dtype)], src.ptr, rows, cols, scale, zmin, zmax, sun[0], sun[1], sun[2],
+    work = workspace("hillshade_shadow", rows, cols)
+    _lib.call("xrs_hillshade_shadow_" + FLOAT_SUFFIX[src.dtype], src.ptr, rows, cols, scale, zmin, zmax, sun[0], sun[1], sun[2],
               int(shadows), work.ptr, out.ptr, stream)
-    if not like_numpy:
-        _lib.call("xrs_stream_sync", stream)                 # the workspace goes back to the pool when this returns
+    settle(stream, like_numpy)
     return finish(out, like_numpy)
 
 
@@ -127,12 +122,10 @@ def _hillshade_shadows(agg, azimuth, angle_altitude, name):
     if fused.current() is not None:
         raise NotImplementedError("hillshade(shadows=True) cannot join a fuse() scope: a shadow ray reads cells far from its "
                                   "own, and the fused pass hands every product one row strip at a time")
-    if isinstance(agg.data, ShardedArray):
-        raise NotImplementedError("hillshade(shadows=True) does not support row-sharded (multi-GPU) DataArray: rays cross shards")
-    if is_dask(agg.data):
-        raise NotImplementedError("hillshade(shadows=True) does not support dask backed DataArray: rays cross chunks")
-    if not isinstance(agg.data, (np.ndarray, DeviceArray)):
-        raise TypeError('Unsupported Array Type: {}'.format(type(agg.data)))
+    refuse_split_backends(
+        agg, None, named=agg.data,
+        sharded="hillshade(shadows=True) does not support row-sharded (multi-GPU) DataArray: rays cross shards",
+        dask="hillshade(shadows=True) does not support dask backed DataArray: rays cross chunks")
     out = _run_shadows(agg.data, azimuth, angle_altitude)
     return DataArray(out, name=name, coords=agg.coords, dims=agg.dims, attrs=agg.attrs)
 

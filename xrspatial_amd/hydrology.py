@@ -36,11 +36,11 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._launch import finish, get_stream
+from ._launch import finish, get_stream, refuse_split_backends, resident, settle, workspace
 from ._xr import DataArray
 from .dataset_support import supports_dataset
-from .device import DeviceArray, to_device_f32
-from .utils import ArrayTypeFunctionMapping, get_dataarray_resolution, not_implemented_func
+from .device import DTYPE_CODE, FLOAT_SUFFIX, DeviceArray, to_device_f32
+from .utils import get_dataarray_resolution
 
 ACCUMULATION, BASINS = 1, 2             # XRS_FLOW_ACCUMULATION / XRS_FLOW_BASINS
 INVALID_CODE, CYCLE = 1, 2              # XRS_FLOW_INVALID_CODE / XRS_FLOW_CYCLE (status word 1)
@@ -48,20 +48,6 @@ TIMED = 1                               # XRS_FLOW_TIMED
 STATUS_WORDS = 80
 MAX_CELLS = 2 ** 32 - 2
 CODES = (0, 1, 2, 4, 8, 16, 32, 64, 128)
-_F32, _F64 = 9, 8                       # XRS_DT_F32 / XRS_DT_F64
-
-
-def _runner(agg, what, run):
-    """`run` for NumPy- and DeviceArray-backed rasters; NotImplementedError for the backends a flow path would cross."""
-    mapper = ArrayTypeFunctionMapping(
-        numpy_func=run, hip_func=run,
-        sharded_func=lambda *args: not_implemented_func(
-            *args, messages=f'{what}() does not support row-sharded (multi-GPU) DataArray'),
-        dask_func=lambda *args: not_implemented_func(*args, messages=f'{what}() does not support dask backed DataArray'))
-    chosen = mapper(agg)
-    if chosen is not run:
-        chosen(agg)
-    return run
 
 
 def _check_raster(data, what):
@@ -89,17 +75,14 @@ def cell_distances(agg):
 # ------------------------------------------------------------------ flow_direction
 def _run_direction(data, cx, cy, dg):
     _lib.require_device()
-    like_numpy = isinstance(data, np.ndarray)
     stream = get_stream()
-    if np.dtype(data.dtype) not in (np.dtype(np.float32), np.dtype(np.float64)):
-        data = (data if like_numpy else data.get(stream)).astype(np.float64)
-    src = DeviceArray.from_numpy(np.ascontiguousarray(data), stream=stream) if isinstance(data, np.ndarray) else data
+    src, like_numpy = resident(data, stream, FLOAT_SUFFIX, np.float64)
     rows, cols = src.shape
     out = DeviceArray((rows, cols), np.float32)
     if rows * cols:
-        _lib.call("xrs_flow_direction", src.ptr, _F32 if src.dtype == np.float32 else _F64, rows, cols, cx, cy, dg, out.ptr, stream)
-        if not like_numpy and src is not data:
-            _lib.call("xrs_stream_sync", stream)                         # the widened copy goes back to the pool
+        _lib.call("xrs_flow_direction", src.ptr, DTYPE_CODE[src.dtype], rows, cols, cx, cy, dg, out.ptr, stream)
+        if src is not data:
+            settle(stream, like_numpy)                                   # the widened copy goes back to the pool
     return finish(out, like_numpy)
 
 
@@ -111,10 +94,10 @@ def flow_direction(agg: DataArray, name: str = 'flow_direction') -> DataArray:
     agg: 2-D DataArray of elevations (or a Dataset: every variable on its own), NumPy- or DeviceArray-backed (the result's
     backend); the cell size comes from `attrs['res']` or the coordinates, as for `slope`.  Returns a float32 DataArray with
     agg's coords, dims and attrs."""
-    run = _runner(agg, 'flow_direction', _run_direction)
+    refuse_split_backends(agg, 'flow_direction')
     rows, cols = _check_raster(agg.data, 'flow_direction')
     cx, cy, dg = cell_distances(agg) if rows * cols else (1.0, 1.0, float(np.sqrt(2.0)))
-    out = run(agg.data, cx, cy, dg)
+    out = _run_direction(agg.data, cx, cy, dg)
     return DataArray(out, name=name, coords=agg.coords, dims=agg.dims, attrs=agg.attrs)
 
 
@@ -127,10 +110,10 @@ def flow_graph(src: DeviceArray, want: int, flags: int = 0, stream=None):
     basin = DeviceArray((rows, cols), np.float64) if want & BASINS else None
     status = (ctypes.c_int64 * STATUS_WORDS)()
     if rows * cols:
-        work = DeviceArray((int(_lib.load().xrs_flow_workspace_bytes(rows, cols, want)),), np.uint8)
+        work = workspace("flow", rows, cols, want)
         _lib.call("xrs_flow_accumulate", src.ptr, rows, cols, work.ptr, acc.ptr if acc else None, basin.ptr if basin else None,
                   status, flags, stream)
-        _lib.call("xrs_stream_sync", stream)                             # the workspace goes back to the pool when this returns
+        settle(stream)
     words = [int(w) for w in status]
     if words[1] & INVALID_CODE:
         raise ValueError("flow direction raster holds a value that is not one of the D8 codes 0, 1, 2, 4, 8, 16, 32, 64, 128")
@@ -148,9 +131,9 @@ def _run_graph(data, want):
 
 
 def _graph_product(flow_dir, name, what, want):
-    run = _runner(flow_dir, what, _run_graph)
+    refuse_split_backends(flow_dir, what)
     _check_raster(flow_dir.data, what)
-    out = run(flow_dir.data, want)
+    out = _run_graph(flow_dir.data, want)
     return DataArray(out, name=name, coords=flow_dir.coords, dims=flow_dir.dims, attrs=flow_dir.attrs)
 
 

@@ -16,7 +16,7 @@ import numpy as np
 
 from . import _lib
 from . import classify as _classify
-from ._launch import get_stream
+from ._launch import get_stream, workspace
 from ._xr import DataArray
 from .dataset_support import supports_dataset
 from .device import DeviceArray
@@ -68,11 +68,10 @@ def jenks_matrices(sorted_sample, k):
     if not 1 <= n <= _MAX_SAMPLE:
         raise _lib.XrsError(f"natural_breaks: the model is fitted on 1 .. 2^24-1 sample values ({n})")
     stream = get_stream()
-    lib = _lib.load()
     data_d = DeviceArray.from_numpy(data, stream=stream)
     limits_d = DeviceArray((n + 1, k + 1), np.float32)
     var_d = DeviceArray((n + 1, k + 1), np.float32)
-    work = DeviceArray((int(lib.xrs_jenks_workspace_bytes(n, k)),), np.uint8)
+    work = workspace("jenks", n, k)
     _lib.call("xrs_jenks_matrices_f32", data_d.ptr, n, k, limits_d.ptr, var_d.ptr, work.ptr, work.nbytes, stream)
     return limits_d.get(stream), var_d.get(stream)
 

@@ -47,10 +47,9 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._launch import finish, get_stream
+from ._launch import finish, get_stream, refuse_split_backends, resident, settle, workspace
 from ._xr import DataArray, Dataset
 from .device import DTYPE_CODE, DeviceArray
-from .utils import ArrayTypeFunctionMapping, not_implemented_func
 
 XRS_LOCAL_MAX_PLANES = 64
 
@@ -104,13 +103,8 @@ def _check_data_vars(raster, data_vars, ref_var=None):
 def _arrays(raster, what, data_vars, ref_var=None, integer_ref=False):
     """The arrays of `data_vars` (and of `ref_var`) after the checks of the module docstring."""
     names = data_vars + ([ref_var] if ref_var is not None else [])
-    mapper = ArrayTypeFunctionMapping(
-        numpy_func=lambda agg: None, hip_func=lambda agg: None,
-        sharded_func=lambda *args: not_implemented_func(
-            *args, messages=f'{what}() does not support row-sharded (multi-GPU) DataArray'),
-        dask_func=lambda *args: not_implemented_func(*args, messages=f'{what}() does not support dask backed DataArray'))
     for name in names:
-        mapper(raster[name])(raster[name])
+        refuse_split_backends(raster[name], what)
     if not data_vars:
         raise ValueError(f"{what}: no data variables")
     if len(data_vars) > XRS_LOCAL_MAX_PLANES:
@@ -133,7 +127,7 @@ def _arrays(raster, what, data_vars, ref_var=None, integer_ref=False):
 
 # ------------------------------------------------------------------ the launches
 def _on_device(arrays, stream):
-    return [a if isinstance(a, DeviceArray) else DeviceArray.from_numpy(np.ascontiguousarray(a), stream=stream) for a in arrays]
+    return [resident(a, stream)[0] for a in arrays]
 
 
 def _plane_table(dev):
@@ -162,7 +156,7 @@ def _run_cells(op, arrays, ref=None):
         _lib.call("xrs_local_cells", op, ptrs, codes, len(dev), ref_dev.ptr if ref_dev is not None else None,
                   DTYPE_CODE[ref_dev.dtype] if ref_dev is not None else 0, out.size, out.ptr, int(out_dtype == np.int64), stream)
         if any(d is not a for d, a in zip(dev + [ref_dev], everything)):
-            _lib.call("xrs_stream_sync", stream)                         # uploaded copies go back to the pool when this returns
+            settle(stream)                                               # uploaded copies go back to the pool when this returns
     return finish(out, like_numpy)
 
 
@@ -178,10 +172,9 @@ def _run_combine(arrays):
         raise ValueError(f"combine: {n} cells, at most 2^31 - 1 are supported")
     key = {}
     if n:
-        lib = _lib.load()
         ptrs, codes = _plane_table(dev)
-        nbytes = int(lib.xrs_local_combine_workspace_bytes(n, len(dev)))
-        work = DeviceArray((nbytes,), np.uint8)
+        work = workspace("local_combine", n, len(dev))
+        nbytes = work.nbytes
         classes = ctypes.c_int64(0)
         _lib.call("xrs_local_combine", ptrs, codes, len(dev), n, work.ptr, nbytes, out.ptr, None, 0, ctypes.byref(classes), stream)
         count = int(classes.value)
@@ -194,7 +187,7 @@ def _run_combine(arrays):
             table = values.get(stream)
             columns = [table[:, j].view(np.float64 if d.dtype.kind == "f" else np.int64).tolist() for j, d in enumerate(dev)]
             key = {i + 1: comb for i, comb in enumerate(zip(*columns))}
-        _lib.call("xrs_stream_sync", stream)
+        settle(stream)
     return finish(out, like_numpy), key
 
 

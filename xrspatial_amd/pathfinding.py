@@ -37,11 +37,11 @@ from typing import Optional, Union
 import numpy as np
 
 from . import _lib
-from ._launch import finish, get_stream
+from ._launch import finish, get_stream, refuse_split_backends, resident, widened, workspace
 from ._xr import DataArray
 from .device import DTYPE_CODE, DeviceArray
-from .proximity import target_array
-from .utils import ArrayTypeFunctionMapping, get_dataarray_resolution, not_implemented_func
+from .proximity import target_array, widen
+from .utils import get_dataarray_resolution
 
 SNAP_START, SNAP_GOAL, NO_WALK, GROUP_SHIFT = 1, 2, 4, 8                 # XRS_ASTAR_*: bits of `snap_flags`
 START_CROSSABLE, GOAL_CROSSABLE, PATH_FOUND = 1, 2, 4                    # XRS_ASTAR_*: bits of the status flags
@@ -69,19 +69,13 @@ def search(data, start, goal, barriers, connectivity, snap_flags=0, walk=True, g
     """One xrs_astar call: (float64 path image on the device, the 8 status words).  `data`: NumPy raster or DeviceArray."""
     _lib.require_device()
     stream = get_stream()
-    dtype = np.dtype(data.dtype)
-    if dtype not in DTYPE_CODE:                                          # bool and float16 widen without loss
-        wider = np.uint8 if dtype == np.bool_ else np.float32 if dtype == np.float16 else None
-        if wider is None:
-            raise TypeError(f"a_star_search: unsupported raster dtype {dtype}")
-        data = (data if isinstance(data, np.ndarray) else data.get(stream)).astype(wider)
-    values, kind = target_array(barriers, data.dtype)
-    src = DeviceArray.from_numpy(np.ascontiguousarray(data), stream=stream) if isinstance(data, np.ndarray) else data
+    data = widened(data, stream, DTYPE_CODE, widen("a_star_search"))
+    values, kind = target_array(barriers, data.dtype)                    # (its TypeError comes before the upload)
+    src, _ = resident(data, stream)
     rows, cols = src.shape
-    work_bytes = int(_lib.load().xrs_astar_workspace_bytes(rows, cols))
+    work = workspace("astar", rows, cols, at_least=1)                    # (a raster beyond 2^30 cells is refused by the call)
     out = DeviceArray((rows, cols), np.float64)
     vals = DeviceArray.from_numpy(values.view(np.float64), stream=stream) if values.size else None
-    work = DeviceArray((max(work_bytes, 1),), np.uint8)                  # (a raster beyond 2^30 cells is refused by the call)
     status = (ctypes.c_int64 * 8)()
     flags = snap_flags | (0 if walk else NO_WALK) | (group << GROUP_SHIFT)
     _lib.call("xrs_astar", src.ptr, DTYPE_CODE[src.dtype], rows, cols, start[0], start[1], goal[0], goal[1],
@@ -124,14 +118,7 @@ def a_star_search(surface: DataArray,
                          "({}, {})".format(y, x))
     if connectivity != 4 and connectivity != 8:
         raise ValueError("Use either 4 or 8-connectivity.")
-    mapper = ArrayTypeFunctionMapping(
-        numpy_func=_run, hip_func=_run,
-        sharded_func=lambda *args: not_implemented_func(
-            *args, messages='a_star_search() does not support row-sharded (multi-GPU) DataArray'),
-        dask_func=lambda *args: not_implemented_func(*args, messages='a_star_search() does not support dask backed DataArray'))
-    run = mapper(surface)
-    if run is not _run:
-        run(surface)
+    refuse_split_backends(surface, 'a_star_search')
 
     start_py, start_px = _get_pixel_id(start, surface, x, y)
     goal_py, goal_px = _get_pixel_id(goal, surface, x, y)
@@ -142,5 +129,5 @@ def a_star_search(surface: DataArray,
         raise ValueError("goal location outside the surface graph.")
 
     snap_flags = (SNAP_START if snap_start else 0) | (SNAP_GOAL if snap_goal else 0)
-    out = run(surface.data, (start_py, start_px), (goal_py, goal_px), np.array(barriers), connectivity, snap_flags)
+    out = _run(surface.data, (start_py, start_px), (goal_py, goal_px), np.array(barriers), connectivity, snap_flags)
     return DataArray(out, coords=surface.coords, dims=surface.dims, attrs=surface.attrs)

@@ -29,11 +29,10 @@ from __future__ import annotations
 import numpy as np
 
 from . import _lib
-from ._launch import finish, get_stream
+from ._launch import finish, get_stream, refuse_split_backends, resident, settle, widened, workspace
 from ._xr import DataArray
 from .dataset_support import supports_dataset
 from .device import DTYPE_CODE, DeviceArray
-from .utils import ArrayTypeFunctionMapping, not_implemented_func
 
 EUCLIDEAN = 0
 GREAT_CIRCLE = 1
@@ -141,19 +140,23 @@ def _prepare(raster, x, y, target_values, max_distance, distance_metric):
 
 
 # ------------------------------------------------------------------ the launch
+def widen(what):
+    """The `widen` of `_launch.widened` for the kernels that read the ten XRS_DT_* dtypes: bool and float16 widen without loss."""
+    def to(dtype):
+        if dtype not in (np.bool_, np.float16):
+            raise TypeError(f"{what}: unsupported raster dtype {dtype}")
+        return np.uint8 if dtype == np.bool_ else np.float32
+    return to
+
+
 def _run(data, xs, ys, target_values, max_distance, metric, mode):
     """A NumPy raster gets NumPy back, a DeviceArray a DeviceArray."""
     _lib.require_device()
     like_numpy = isinstance(data, np.ndarray)
     stream = get_stream()
-    dtype = np.dtype(data.dtype)
-    if dtype not in DTYPE_CODE:                                          # bool and float16 widen without loss
-        wider = np.uint8 if dtype == np.bool_ else np.float32 if dtype == np.float16 else None
-        if wider is None:
-            raise TypeError(f"proximity: unsupported raster dtype {dtype}")
-        data = (data if like_numpy else data.get(stream)).astype(wider)
-    values, kind = target_array(target_values, data.dtype)
-    src = DeviceArray.from_numpy(np.ascontiguousarray(data), stream=stream) if isinstance(data, np.ndarray) else data
+    data = widened(data, stream, DTYPE_CODE, widen("proximity"))
+    values, kind = target_array(target_values, data.dtype)              # (its TypeError comes before the upload)
+    src, _ = resident(data, stream)
     rows, cols = src.shape
     out = DeviceArray((rows, cols), np.float32)
     if rows * cols:
@@ -165,26 +168,17 @@ def _run(data, xs, ys, target_values, max_distance, metric, mode):
         aux = DeviceArray.from_numpy(np.concatenate(parts), stream=stream)
         gc = aux.ptr + 8 * (cols + rows) if metric == GREAT_CIRCLE else None
         vals = aux.ptr + 8 * (sum(p.size for p in parts) - values.size) if values.size else None
-        work = DeviceArray((int(_lib.load().xrs_proximity_workspace_bytes(rows, cols)),), np.uint8)
+        work = workspace("proximity", rows, cols)
         _lib.call("xrs_proximity", src.ptr, DTYPE_CODE[src.dtype], rows, cols, aux.ptr, aux.ptr + 8 * cols, gc, vals, kind,
                   int(values.size), max_distance, metric, mode, work.ptr, out.ptr, stream)
-        if not like_numpy:
-            _lib.call("xrs_stream_sync", stream)                         # the workspace goes back to the pool when this returns
+        settle(stream, like_numpy)
     return finish(out, like_numpy)
 
 
 def _process(raster, x, y, target_values, max_distance, distance_metric, mode):
-    what = ("proximity", "allocation", "direction")[mode]
-    mapper = ArrayTypeFunctionMapping(
-        numpy_func=_run, hip_func=_run,
-        sharded_func=lambda *args: not_implemented_func(
-            *args, messages=f'{what}() does not support row-sharded (multi-GPU) DataArray'),
-        dask_func=lambda *args: not_implemented_func(*args, messages=f'{what}() does not support dask backed DataArray'))
-    run = mapper(raster)
-    if run is not _run:
-        run(raster)
+    refuse_split_backends(raster, ("proximity", "allocation", "direction")[mode])
     metric, max_distance, xs, ys = _prepare(raster, x, y, target_values, max_distance, distance_metric)
-    out = run(raster.data, xs, ys, target_values, max_distance, metric, mode)
+    out = _run(raster.data, xs, ys, target_values, max_distance, metric, mode)
     return DataArray(out, coords=raster.coords, dims=raster.dims, attrs=raster.attrs)
 
 

@@ -10,9 +10,10 @@ from __future__ import annotations
 
 import numpy as np
 
+from ._launch import refuse_split_backends
 from ._xr import DataArray
 from .perlin import MODE_TERRAIN, check_dtype, check_lattice, run
-from .utils import ArrayTypeFunctionMapping, get_dataarray_resolution, not_implemented_func
+from .utils import get_dataarray_resolution
 
 N_OCTAVES = 16
 WATER_LINE = 0.3                          # `data[data < 0.3] = 0`, compared in the data's dtype
@@ -64,13 +65,8 @@ def generate_terrain(agg, x_range=(0, 500), y_range=(0, 500), seed=10, zfactor=4
     y_range_scaled = (_scale(y_range[0], full_yrange, (0.0, 1.0)), _scale(y_range[1], full_yrange, (0.0, 1.0)))
     check_lattice("generate_terrain", x_range_scaled, y_range_scaled, agg.shape, N_OCTAVES)
 
-    mapper = ArrayTypeFunctionMapping(
-        numpy_func=_run_terrain, hip_func=_run_terrain,
-        sharded_func=lambda *args: not_implemented_func(
-            *args, messages='generate_terrain() does not support row-sharded (multi-GPU) DataArray'),
-        dask_func=lambda *args: not_implemented_func(
-            *args, messages='generate_terrain() does not support dask backed DataArray'))
-    out = mapper(agg)(agg.data, int(seed), x_range_scaled, y_range_scaled, zfactor)
+    refuse_split_backends(agg, 'generate_terrain')
+    out = _run_terrain(agg.data, int(seed), x_range_scaled, y_range_scaled, zfactor)
 
     coords = {'y': cell_centres(y_range[0], y_range[1], height), 'x': cell_centres(x_range[0], x_range[1], width)}
     result = DataArray(out, name=name, coords=coords, dims=('y', 'x'))

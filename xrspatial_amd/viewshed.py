@@ -40,15 +40,13 @@ from __future__ import annotations
 import numpy as np
 
 from . import _lib
-from ._launch import finish, get_stream
+from ._launch import finish, get_stream, refuse_split_backends, resident, settle, workspace
 from ._xr import DataArray
-from .device import DeviceArray
-from .utils import ArrayTypeFunctionMapping, not_implemented_func
+from .device import FLOAT_SUFFIX, DeviceArray
 
 OBS_ELEV = 0
 TARGET_ELEV = 0
 INVISIBLE = -1
-_SUFFIX = {np.dtype(np.float32): "f32", np.dtype(np.float64): "f64"}
 
 
 # ------------------------------------------------------------------ argument checks and the viewpoint (before any device work)
@@ -87,18 +85,14 @@ def viewpoint(raster, x, y):
 def _run(data, row, col, observer_elev, target_elev, ew_res, ns_res):
     """A NumPy raster gets NumPy back, a DeviceArray a DeviceArray."""
     _lib.require_device()
-    like_numpy = isinstance(data, np.ndarray)
     stream = get_stream()
-    if np.dtype(data.dtype) not in _SUFFIX:                  # integers, bool, float16: float64, as the reference casts
-        data = (data if like_numpy else data.get(stream)).astype(np.float64)
-    src = DeviceArray.from_numpy(data, stream=stream) if isinstance(data, np.ndarray) else data
+    src, like_numpy = resident(data, stream, FLOAT_SUFFIX, np.float64)      # integers, bool, float16: float64, as the reference casts
     rows, cols = src.shape
     out = DeviceArray((rows, cols), np.float64)
-    work = DeviceArray((int(_lib.load().xrs_viewshed_workspace_bytes(rows, cols)),), np.uint8)
-    _lib.call("xrs_viewshed_" + _SUFFIX[src.dtype], src.ptr, rows, cols, row, col, float(observer_elev), float(target_elev),
+    work = workspace("viewshed", rows, cols)
+    _lib.call("xrs_viewshed_" + FLOAT_SUFFIX[src.dtype], src.ptr, rows, cols, row, col, float(observer_elev), float(target_elev),
               float(ew_res), float(ns_res), work.ptr, out.ptr, stream)
-    if not like_numpy:
-        _lib.call("xrs_stream_sync", stream)                 # the workspace goes back to the pool when this returns
+    settle(stream, like_numpy)
     return finish(out, like_numpy)
 
 
@@ -112,11 +106,10 @@ def _run_mesh(data, row, col, observer_elev, target_elev, ew_res, ns_res):
     if not (np.isfinite(observer_elev * scale) and np.isfinite(target_elev * scale)):
         raise ValueError("viewshed(method='mesh'): observer_elev and target_elev overflow the mesh's height scale")
     out = DeviceArray((rows, cols), np.float32)
-    work = DeviceArray((int(_lib.load().xrs_viewshed_mesh_workspace_bytes(rows, cols)),), np.uint8)
-    _lib.call("xrs_viewshed_mesh_" + _SUFFIX[np.dtype(src.dtype)], src.ptr, rows, cols, scale, zmin, zmax, row, col,
+    work = workspace("viewshed_mesh", rows, cols)
+    _lib.call("xrs_viewshed_mesh_" + FLOAT_SUFFIX[src.dtype], src.ptr, rows, cols, scale, zmin, zmax, row, col,
               float(observer_elev), float(target_elev), float(ew_res), float(ns_res), work.ptr, out.ptr, stream)
-    if not like_numpy:
-        _lib.call("xrs_stream_sync", stream)                 # the workspace goes back to the pool when this returns
+    settle(stream, like_numpy)
     return finish(out, like_numpy)
 
 
@@ -148,12 +141,8 @@ def viewshed(raster, x, y, observer_elev=OBS_ELEV, target_elev=TARGET_ELEV, meth
     if not (np.isfinite(ew_res) and np.isfinite(ns_res)):
         raise ValueError("viewshed: the raster's coordinates are not finite")
     run = _run_mesh if method == "mesh" else _run
-    mapper = ArrayTypeFunctionMapping(
-        numpy_func=run, hip_func=run,
-        sharded_func=lambda *args: not_implemented_func(
-            *args, messages='viewshed() does not support row-sharded (multi-GPU) DataArray'),
-        dask_func=lambda *args: not_implemented_func(*args, messages='viewshed() does not support dask backed DataArray'))
-    out = mapper(raster)(raster.data, row, col, observer_elev, target_elev, ew_res, ns_res)
+    refuse_split_backends(raster, 'viewshed')
+    out = run(raster.data, row, col, observer_elev, target_elev, ew_res, ns_res)
     if method == "mesh":
         return DataArray(out, name="viewshed", coords=raster.coords, dims=raster.dims, attrs=raster.attrs)
     return DataArray(out, coords=raster.coords, dims=raster.dims, attrs=raster.attrs)

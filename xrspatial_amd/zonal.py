@@ -15,7 +15,7 @@ import numpy as np
 import pandas as pd
 
 from . import _lib
-from ._launch import get_stream
+from ._launch import finish, get_stream, refuse_split_backends, resident, settle, workspace
 from ._xr import DataArray, Dataset
 from .device import DTYPE_CODE, DeviceArray
 from .sharded import ShardedArray, ShardedStack, same_layout
@@ -361,22 +361,20 @@ def zonal_majority(zone_idx, values, n_zones, nodata_values=None, counts=None):
         # continuous values: route the cells by (zone, hash of the value) into LDS-sized parts and count there
         # (csrc/zonal_mode.hip); the entry behind the zones counts parts that did not fit -- then, and only then, sort
         out = DeviceArray((n_zones + 1,), np.float64)
-        nbytes = int(_lib.load().xrs_zonal_mode_workspace_bytes(vdev.size, n_zones, int(f64)))
-        work = DeviceArray((nbytes,), np.uint8)
+        work = workspace("zonal_mode", vdev.size, n_zones, int(f64))
         cdev = None
         if counts is not None and len(counts) == n_zones and int(np.max(counts, initial=0)) < (1 << 32):
             cdev = DeviceArray.from_numpy(np.ascontiguousarray(counts, dtype=np.uint32))
         _lib.call("xrs_zonal_mode_f64" if f64 else "xrs_zonal_mode_f32", zdev.ptr, vdev.ptr, vdev.size, n_zones, nodata,
-                  int(has_nodata), cdev.ptr if cdev is not None else None, work.ptr, nbytes, out.ptr, stream)
+                  int(has_nodata), cdev.ptr if cdev is not None else None, work.ptr, work.nbytes, out.ptr, stream)
         res = out.get(stream)
         del work
         if res[n_zones] == 0:
             return res[:n_zones]
     out = DeviceArray((n_zones,), np.float64)
-    nbytes = int(_lib.load().xrs_zonal_majority_workspace_bytes(vdev.size, n_zones, int(f64)))
-    work = DeviceArray((nbytes,), np.uint8)
+    work = workspace("zonal_majority", vdev.size, n_zones, int(f64))
     _lib.call("xrs_zonal_majority_f64" if f64 else "xrs_zonal_majority_f32", zdev.ptr, vdev.ptr, vdev.size,
-              n_zones, nodata, int(has_nodata), work.ptr, nbytes, out.ptr, stream)
+              n_zones, nodata, int(has_nodata), work.ptr, work.nbytes, out.ptr, stream)
     return out.get(stream)
 
 
@@ -389,13 +387,12 @@ def zonal_grouped_values(zone_idx, values, n_zones, nodata_values=None):
     zdev, vdev = _stage(zone_idx, values)
     f64 = vdev.dtype == np.float64
     n = int(vdev.size)
-    nbytes = int(_lib.load().xrs_zonal_majority_workspace_bytes(n, max(n_zones, 1), int(f64)))
-    work = DeviceArray((nbytes,), np.uint8)
+    work = workspace("zonal_majority", n, max(n_zones, 1), int(f64))
     out = DeviceArray((max(n, 1),), vdev.dtype)
     has_nodata = nodata_values is not None
     nodata = float(nodata_values) if has_nodata else 0.0
     _lib.call("xrs_zonal_group_f64" if f64 else "xrs_zonal_group_f32", zdev.ptr, vdev.ptr, n, n_zones, nodata,
-              int(has_nodata), work.ptr, nbytes, out.ptr, stream)
+              int(has_nodata), work.ptr, work.nbytes, out.ptr, stream)
     return out, vdev.dtype
 
 
@@ -1010,12 +1007,11 @@ def regions(raster, neighborhood=4, name='regions'):
     if neighborhood not in (4, 8):
         raise ValueError("`neighborhood` value must be either 4 or 8)")
     data = raster.data
-    if isinstance(data, ShardedArray):
-        raise NotImplementedError("zonal.regions of a row-sharded (multi-GPU) raster: merging regions across shards is "
-                                  "not implemented; gather the raster on one GPU")
-    if is_dask(data):
-        raise NotImplementedError("zonal.regions of a dask-backed raster: the reference has no dask path either; "
-                                  "compute the raster first")
+    refuse_split_backends(
+        raster, None, others=True,
+        sharded="zonal.regions of a row-sharded (multi-GPU) raster: merging regions across shards is not implemented; gather "
+                "the raster on one GPU",
+        dask="zonal.regions of a dask-backed raster: the reference has no dask path either; compute the raster first")
     if len(data.shape) != 2:
         raise ValueError(f"zonal.regions: expected a 2D raster, got {len(data.shape)} dimensions")
     dtype = np.dtype(data.dtype)
@@ -1026,13 +1022,10 @@ def regions(raster, neighborhood=4, name='regions'):
         raise ValueError(f"zonal.regions: {rows} x {cols} cells exceed the 2**32 - 1 cells this backend labels")
     _lib.require_device()
     stream = get_stream()
-    if isinstance(data, DeviceArray):
-        dev, like_numpy = data, False
-    else:
-        dev, like_numpy = DeviceArray.from_numpy(np.ascontiguousarray(data), stream=stream), True
+    dev, like_numpy = resident(data, stream)
     out = DeviceArray((rows, cols), dtype)
     if rows * cols:
-        work = DeviceArray((_lib.load().xrs_regions_workspace_bytes(rows, cols),), np.uint8)
+        work = workspace("regions", rows, cols)
         n_new = ctypes.c_uint64(0)
         _lib.call("xrs_regions_link", dev.ptr, DTYPE_CODE[dtype], rows, cols, neighborhood, work.ptr, ctypes.byref(n_new),
                   stream)
@@ -1041,6 +1034,5 @@ def regions(raster, neighborhood=4, name='regions'):
             raise ValueError(f"zonal.regions: the labels of this raster run up to {n_new.value}, more than {dtype} holds "
                              f"exactly (at most {limit}); cast the raster to {wider} first")
         _lib.call("xrs_regions_label", dev.ptr, DTYPE_CODE[dtype], rows, cols, neighborhood, work.ptr, out.ptr, stream)
-        _lib.call("xrs_stream_sync", stream)            # the workspace goes back to the pool
-    result = out.get(stream) if like_numpy else out
-    return DataArray(result, name=name, dims=raster.dims, coords=raster.coords, attrs=raster.attrs)
+        settle(stream)                                  # the workspace goes back to the pool
+    return DataArray(finish(out, like_numpy), name=name, dims=raster.dims, coords=raster.coords, attrs=raster.attrs)
