@@ -580,10 +580,24 @@ int xrs_viewshed_mesh_probe_f64(const double *data_dev, int64_t rows, int64_t co
  *   gc_dev     GREAT_CIRCLE only (else may be null): np.radians(xs) (cols), np.radians(ys) (rows), np.cos(np.radians(ys))
  *              (rows), one after the other.
  *   metric     0 EUCLIDEAN, 1 GREAT_CIRCLE, 2 MANHATTAN (the reference's codes).
- *   mode       0 proximity, 1 allocation, 2 direction: one float32 plane into out_dev; 3: all three planes, in that order.
- *              | XRS_PROX_SCAN_ONLY: only the row scan (left / right nearest target columns and the list of non-empty rows
- *              into work_dev); | XRS_PROX_SEARCH_ONLY: only the search, on a workspace that holds the same raster's scan.
- *   work_dev   xrs_proximity_workspace_bytes(rows, cols) bytes, caller-owned.
+ *   mode       0 proximity, 1 allocation, 2 direction: one float32 plane of rows * cols into out_dev; 3: all three planes, in
+ *              that order, 3 * rows * cols floats, each bit-equal to what modes 0, 1, 2 write.
+ *              | XRS_PROX_SCAN_ONLY: only the row scan into work_dev; max_distance, metric and the product bits are not
+ *              read, out_dev is not written and may be null.  | XRS_PROX_SEARCH_ONLY: only the search, on a workspace that
+ *              holds the same raster's scan; work_dev is read only, out_dev must not be null.  Both bits at once, or any bit
+ *              beside these two and the product, are refused.
+ *   work_dev   xrs_proximity_workspace_bytes(rows, cols) bytes, caller-owned.  Its layout is part of the ABI (SEARCH_ONLY
+ *              consumes it); with up256(n) = n rounded up to a multiple of 256, byte offsets from work_dev:
+ *                left   0                                    int32[rows * cols]  largest target column <= j of the row, -1: none
+ *                right  up256(4 rows cols)                   int32[rows * cols]  smallest target column > j, -1: none
+ *                flag   2 up256(4 rows cols)                 int32[rows]         1 where the row holds a target, else 0
+ *                list   flag + up256(4 rows)                 int32[rows]         the rows with a target, ascending; only the
+ *                                                                                first `count` entries are written
+ *                count  list + up256(4 rows)                 int32[1]            their number
+ *              and the size is count + 256.  Nothing outside these arrays is written.
+ * Ties: of several targets at the smallest float32 distance those in rows <= i come first, there the first in row-major
+ * order, among rows > i the last.  EUCLIDEAN and MANHATTAN follow that at every cell, runs of equidistant targets inside one
+ * row (long thin cells, distances that underflow) included; GREAT_CIRCLE names the nearest of such a run on either side.
  * Three launches on the stream (scan, row list, search); cells without a target within max_distance are NaN. */
 enum { XRS_PROX_VALUES_F64 = 0, XRS_PROX_VALUES_I64 = 1, XRS_PROX_VALUES_U64 = 2 };
 enum { XRS_PROX_SCAN_ONLY = 16, XRS_PROX_SEARCH_ONLY = 32 };

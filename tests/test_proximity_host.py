@@ -257,6 +257,16 @@ def test_abi_refuses_bad_arguments_before_device_work():
                      (dict(kind=3), "kind"), (dict(kind=1, dtype=8), "float raster"), (dict(data=None), "null"), (dict(xs=None), "null"),
                      (dict(ys=None), "null"), (dict(work=None), "null"), (dict(out=None), "null"), (dict(n=2), "null"),
                      (dict(metric=1), "radians"), (dict(md=float("nan")), "NaN"), (dict(cols=1 << 31), "too large"),
-                     (dict(rows=1 << 30, cols=1 << 12), "too large")):
+                     (dict(rows=1 << 30, cols=1 << 12), "too large"),
+                     (dict(mode=3 | 16 | 32), "unknown mode"), (dict(mode=16 | 32), "unknown mode"),      # both halves left out
+                     (dict(mode=3 | 64), "unknown mode"), (dict(mode=8), "unknown mode"), (dict(mode=-1), "unknown mode"),
+                     (dict(mode=1 | 256), "unknown mode"),
+                     (dict(mode=32, out=None), "null"), (dict(mode=3 | 32, out=None), "null"),             # SEARCH_ONLY writes planes
+                     (dict(mode=16, out=None, work=None), "null"), (dict(mode=16, out=None, cols=1 << 31), "too large")):
         assert call(**kw) != 0 and text in _lib.last_error(), (kw, _lib.last_error())
     assert call(rows=0) == 0 and call(cols=0, data=None, work=None, out=None) == 0       # nothing to do
+    # SCAN_ONLY writes no plane: a null out_dev is accepted.  Without a device that shows in the NEXT check being the one that
+    # refuses (max_distance is looked at after the pointers); tests/test_gpu_proximity_abi.py runs every scan that way.
+    for mode in (16, 3 | 16):
+        assert call(mode=mode, out=None, md=float("nan")) != 0 and "NaN" in _lib.last_error(), mode
+    assert call(mode=32, out=None, md=float("nan")) != 0 and "null" in _lib.last_error()

@@ -19,8 +19,13 @@
 //            cell's place in the list outwards, above and below in turn, two candidates per row.  A side is finished for a
 //            lane once the row's lower bound (|dy|; R |dlat| (1 - 1e-12) for haversine) as float32 is strictly above the best
 //            d32 (rounding is monotonic, so no target of that row can tie) or its square is beyond max_distance^2.
-// Known limit: two targets of one row on one side of j share a d32 only beyond ~2^11.5 cells; the search sees the nearer one
-// (proximity is unaffected, allocation / direction may name the other of two float32-equidistant targets).
+//            Several targets of one row on one side of j can share a d32: with square cells only beyond ~2^11.5 cells, with
+//            long thin cells (or coordinates so small that d32 underflows) whole runs of them.  Rule 3 then names the far end
+//            of the run, not the nearest: EUCLIDEAN and MANHATTAN move the winner there after the walk (tied_end).
+// Known limit: GREAT_CIRCLE does not extend (the device's sin / asin are not the reference's to the last bit, so a float32 tie
+// there is not the rule's tie anyway): proximity is unaffected, allocation / direction name the nearest of the float32-
+// equidistant targets of a row side where the rule may name another.
+// Workspace (ABI, include/xrs_hip.h): left | right | flag | list | count, each part rounded up to 256 bytes (plan()).
 // Contraction is off for the whole file: dx * dx + dy * dy must round as the reference's.
 #include "xrs_common.h"
 #include "value_match.h"
@@ -203,6 +208,71 @@ __global__ void __launch_bounds__(SPAN) proximity_search_kernel(const Search p) 
     int best_r = -1, best_c = -1;
     bool open_up = valid, open_dn = valid;
 
+    auto d32_of = [&](int r, int c) -> float {
+        double d;
+        if (METRIC == EUCLIDEAN) {
+            const double dx = p.xs[c] - x2, dy = p.ys[r] - y2;
+            d = sqrt(dx * dx + dy * dy);
+        } else if (METRIC == MANHATTAN) {
+            const double dx = p.xs[c] - x2, dy = p.ys[r] - y2;
+            d = fabs(dx) + fabs(dy);
+        } else {
+            const double dlon = lon2 - p.lon[c], dlat = lat2 - p.lat[r];
+            const double sa = sin(dlat / 2.0), so = sin(dlon / 2.0);
+            const double a = sa * sa + p.coslat[r] * cos2 * (so * so);
+            d = 12756274.0 * asin(sqrt(a));
+        }
+        return (float)d;
+    };
+
+    // rule 3 inside the winner's row (EUCLIDEAN / MANHATTAN), once per cell after the walk.  The keys of two rows are ordered by
+    // the rows alone, so which row wins does not depend on which of its equidistant targets stands for it; the walk keeps the
+    // nearest.  The columns of row r that share its d32 form one run, as d32 is monotonic in |c - j| in the very arithmetic
+    // above.  Above (r <= i) the rule names the run's leftmost target: beyond the nearest-left candidate (a winner right of j
+    // means that nothing at or left of j ties).  Below it names the rightmost, beyond the nearest-right one.  Whether there is
+    // a run at all is decided in steps of rising cost: may_tie on the next column, the next target's d32, and only then the
+    // run's far end by bisection over the column index and one step back to the first target inside it through left / right:
+    // log2(cols) distances, never the chain of targets link by link.
+    //
+    // may_tie: can column `next` (one further from j than c) round to c's d32?  Necessary, not sufficient, and without a
+    // sqrt.  Equal float32 values in the normal range lie within one ulp, at most 2^-23 relative, so the float64 distances b >= a
+    // have b / a < 1 + 2^-23 < 1 + 1.2e-7 (their squares: < 1 + 2^-22 + 2^-46 < 1 + 2.4e-7; the float64 roundings of a and b, 1e-16,
+    // vanish in the margin).  Outside the normal range -- below 2^-126 the spacing is absolute, above 2^127 everything is inf
+    // -- the exact comparison decides.
+    auto may_tie = [&](int r, int c, int next) -> bool {
+        const double dy = p.ys[r] - y2, dx = p.xs[c] - x2, dn = p.xs[next] - x2;
+        if (METRIC == EUCLIDEAN) {
+            const double a = dx * dx + dy * dy, b = dn * dn + dy * dy;
+            return b - a <= a * 2.4e-7 || b < 0x1p-250 || !(b < 0x1p254);
+        }
+        const double a = fabs(dx) + fabs(dy), b = fabs(dn) + fabs(dy);
+        return b - a <= a * 1.2e-7 || b < 0x1p-125 || !(b < 0x1p127);
+    };
+    auto tied_end = [&](int r, long at, int c, float d32, bool above) -> int {
+        if (above) {
+            if (c > j || c == 0 || !may_tie(r, c, c - 1)) return c;
+            const int nb = p.left[at + c - 1];
+            if (nb < 0 || d32_of(r, nb) != d32) return c;
+            int lo = 0, hi = nb;                                         // d32_of(hi) == d32: the smallest such column
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (d32_of(r, mid) == d32) hi = mid; else lo = mid + 1;
+            }
+            const int e = p.left[at + lo] == lo ? lo : p.right[at + lo];
+            return e >= 0 && e < nb ? e : nb;                            // (inside [lo, nb] whatever the planes hold)
+        }
+        if (c <= j || c == (int)p.cols - 1 || !may_tie(r, c, c + 1)) return c;
+        const int nb = p.right[at + c];
+        if (nb < 0 || d32_of(r, nb) != d32) return c;
+        int lo = nb, hi = (int)p.cols - 1;                               // d32_of(lo) == d32: the largest such column
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (d32_of(r, mid) == d32) lo = mid; else hi = mid - 1;
+        }
+        const int e = p.left[at + lo];
+        return e > nb ? e : nb;                                          // (inside [nb, lo])
+    };
+
     auto visit = [&](int r, bool &open, bool above) {
         float bound;
         if (METRIC == GREAT_CIRCLE) bound = (float)(6378137.0 * fabs(lat2 - p.lat[r]) * (1.0 - 1e-12));
@@ -218,20 +288,7 @@ __global__ void __launch_bounds__(SPAN) proximity_search_kernel(const Search p) 
         for (int k = 0; k < (METRIC == GREAT_CIRCLE ? 4 : 2); ++k) {
             const int c = cand[k];
             if (c < 0) continue;
-            double d;
-            if (METRIC == EUCLIDEAN) {
-                const double dx = p.xs[c] - x2, dy = p.ys[r] - y2;
-                d = sqrt(dx * dx + dy * dy);
-            } else if (METRIC == MANHATTAN) {
-                const double dx = p.xs[c] - x2, dy = p.ys[r] - y2;
-                d = fabs(dx) + fabs(dy);
-            } else {
-                const double dlon = lon2 - p.lon[c], dlat = lat2 - p.lat[r];
-                const double sa = sin(dlat / 2.0), so = sin(dlon / 2.0);
-                const double a = sa * sa + p.coslat[r] * cos2 * (so * so);
-                d = 12756274.0 * asin(sqrt(a));
-            }
-            const float d32 = (float)d;
+            const float d32 = d32_of(r, c);
             const long key = above ? at + c : 2 * cells - (at + c);
             if (d32 < best || (d32 == best && key < best_key)) { best = d32; best_key = key; best_r = r; best_c = c; }
         }
@@ -250,6 +307,8 @@ __global__ void __launch_bounds__(SPAN) proximity_search_kernel(const Search p) 
         }
     }
     if (!valid) return;
+    if (METRIC != GREAT_CIRCLE && p.mode != MODE_PROXIMITY && best_r >= 0)   // (the distance is the same wherever in the run)
+        best_c = tied_end(best_r, (long)best_r * p.cols, best_c, best, best_r <= i);
 
     const float s = best * best;
     const bool kept = best_r >= 0 && (p.max2 >= (double)s);

@@ -8,7 +8,10 @@ computes the minimum itself (csrc/proximity.hip), by this rule f
   1. a target is a cell that is non-zero and finite (`target_values` empty) or equals one of `target_values` under NumPy's `==`;
   2. its distance is the reference's `_distance(xs[c], x2, ys[r], y2, metric)`: float64 on the coordinate values, then float32;
   3. the smallest float32 distance wins; of equal ones targets in rows r <= i come first, among them the first in row-major
-     order, among rows r > i the last in row-major order (the order in which the sweep meets them);
+     order, among rows r > i the last in row-major order (the order in which the sweep meets them).  EUCLIDEAN and MANHATTAN
+     follow that at every cell, also where a whole run of targets in one row shares a float32 distance (long thin cells,
+     distances that underflow); GREAT_CIRCLE names the nearest target of such a run on either side of the cell, where the
+     rule may name another (`proximity` is the same either way);
   4. with s = d32 * d32 in float32 the cell is kept if float64(max_distance)**2 >= s, else all three products are NaN;
   5. proximity = float32(sqrt(float64(s))), allocation = float32(raster[r, c]), direction = the reference's `_calc_direction`.
 
