@@ -752,6 +752,31 @@ size_t xrs_flow_workspace_bytes(int64_t rows, int64_t cols, int want);
 int xrs_flow_accumulate(const float *dir_dev, int64_t rows, int64_t cols, void *work_dev, double *acc_out_dev, double *basin_out_dev,
                         int64_t *status_host, int flags, void *stream);
 
+/* Depression fill and flat resolution in front of D8 (the rules: xrspatial_amd/hydrology.py).
+ *   xrs_fill        out_dev (z_dev's dtype, another plane than z_dev) = for every cell the least level a path of non-NaN cells
+ *              to a rim cell can be held to: z at rim cells (a neighbour outside the raster or NaN), NaN at NaN cells, else the
+ *              fixed point of W = max(z, min over the eight neighbours of W) reached from +inf.  Comparisons only.
+ *   xrs_flow_flats  code_dev: xrs_flow_direction's result for z_dev, updated in place.  A cell with code 0 that is no rim cell
+ *              takes the code of its first neighbour (order E, SE, S, SW, W, NW, N, NE) of equal elevation that is one step
+ *              nearer, through cells of that elevation, to a cell with a code or a rim cell; without such a cell it keeps 0.
+ *   `dtype`: XRS_DT_F32 or XRS_DT_F64, at most XRS_FLOW_MAX_CELLS cells.  Both relax a plane tile by tile (XRS_FILL_TILE cells
+ *   square, in LDS), the tiles coloured 2 x 2 and each colour a launch of its own, in rounds; a round launches the tiles with a
+ *   neighbour that changed in the round before; the host reads the count of changed cells after every round (the call waits
+ *   for the stream then) and stops at the first 0.  More than rows * cols + 1 rounds are an error.
+ *   work_dev   caller-owned; xrs_fill_workspace_size / xrs_flow_flats_workspace_size write its bytes to *bytes_out (0 for an
+ *              empty raster or one beyond the cell limit) and return 0, or non-zero for a null pointer.
+ *   status_host HOST array of XRS_FILL_STATUS_WORDS words: [0] rounds run, the last one without a change included; [1] tiles
+ *              launched in all; [2], [3] nanoseconds of the first and (flats) the last launch; for the first
+ *              XRS_FILL_STATUS_ROUNDS rounds k: [8 + k] cells that changed, [8 + ROUNDS + k] tiles launched, [8 + 2 ROUNDS + k]
+ *              nanoseconds.  The times only with XRS_FILL_TIMED in `flags` (a stream sync around every launch). */
+enum { XRS_FILL_TIMED = 1, XRS_FILL_TILE = 64, XRS_FILL_STATUS_ROUNDS = 80, XRS_FILL_STATUS_WORDS = 256 };
+int xrs_fill_workspace_size(int64_t rows, int64_t cols, uint64_t *bytes_out);
+int xrs_fill(const void *z_dev, int dtype, int64_t rows, int64_t cols, void *out_dev, void *work_dev, int64_t *status_host, int flags,
+             void *stream);
+int xrs_flow_flats_workspace_size(int64_t rows, int64_t cols, uint64_t *bytes_out);
+int xrs_flow_flats(const void *z_dev, int dtype, int64_t rows, int64_t cols, float *code_dev, void *work_dev, int64_t *status_host,
+                   int flags, void *stream);
+
 /* multispectral.true_color (xrspatial/multispectral.py:1334-1495).
  *   xrs_nan_minmax_f32: minmax_dev[0..1] = np.nanmin / np.nanmax of a float32 plane (NaN, NaN if it holds no number);
  *   xrs_true_color_u8:  rgba[i] = { stretch(red), stretch(green), stretch(blue), alpha } with

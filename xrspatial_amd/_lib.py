@@ -225,6 +225,10 @@ _PROTOTYPES = {
     "xrs_flow_direction": [c_void_p, c_int, c_int64, c_int64, c_double, c_double, c_double, c_void_p, c_void_p],
     "xrs_flow_workspace_bytes": [c_int64, c_int64, c_int],
     "xrs_flow_accumulate": [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int64), c_int, c_void_p],
+    "xrs_fill_workspace_size": [c_int64, c_int64, ctypes.POINTER(ctypes.c_uint64)],
+    "xrs_fill": [c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, ctypes.POINTER(c_int64), c_int, c_void_p],
+    "xrs_flow_flats_workspace_size": [c_int64, c_int64, ctypes.POINTER(ctypes.c_uint64)],
+    "xrs_flow_flats": [c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, ctypes.POINTER(c_int64), c_int, c_void_p],
     "xrs_comm_unique_id": [c_void_p],
     "xrs_comm_init_rank": [ctypes.POINTER(c_void_p), c_void_p, c_int, c_int],
     "xrs_comm_destroy": [c_void_p],
@@ -263,7 +267,12 @@ def load():
 
 
 def workspace_bytes(name: str, *args) -> int:
-    """What `xrs_<name>_workspace_bytes(*args)` answers: the bytes of device scratch the call of that name needs."""
+    """What `xrs_<name>_workspace_bytes(*args)` answers: the bytes of device scratch the call of that name needs.  The entries
+    named `xrs_<name>_workspace_size` return a status like every other entry point and write the bytes through a last pointer."""
+    if f"xrs_{name}_workspace_size" in _PROTOTYPES:
+        size = ctypes.c_uint64(0)
+        call(f"xrs_{name}_workspace_size", *args, ctypes.byref(size))
+        return int(size.value)
     return int(getattr(load(), f"xrs_{name}_workspace_bytes")(*args))
 
 

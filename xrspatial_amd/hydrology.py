@@ -1,6 +1,17 @@
-"""flow_direction, flow_accumulation, basins: D8 hydrology.  The reference (0.5.3) has no hydrology code, so the result is a
-written rule (csrc/hydrology.hip; stated in NumPy by tests/hydrology_oracle.py), and every output is an integer
-code or a count: the tests compare bit for bit.
+"""fill, flow_direction, flow_accumulation, basins: D8 hydrology.  The reference (0.5.3) has no hydrology code, so the result is a
+written rule (csrc/hydrology.hip and csrc/hydrology_fill.hip; stated in NumPy by tests/hydrology_oracle.py
+and tests/hydrology_fill_oracle.py), and every output is an input value, an integer code or a count: the tests compare bit for bit.
+
+fill.  The neighbours are the eight below.  A rim cell is a non-NaN cell with a neighbour outside the raster or NaN: water leaves
+the raster there.
+  1. a NaN cell gives NaN;
+  2. a rim cell keeps its value;
+  3. every other cell gets W(c) = the minimum, over all 8-connected paths of non-NaN cells from c to a rim cell, of the largest z
+     on the path (both ends included): the fixed point of W(c) = max(z(c), min_n W(n)) reached from +inf at non-rim cells;
+  4. only comparisons are made: every output value is an input value, +-inf are ordinary values, and which of -0.0 / +0.0
+     comes out is not specified;
+  5. float32 gives float32, float64 float64 (read in place); every other numeric dtype is cast to float64 on the host;
+  6. with fewer than 3 rows or columns every cell is a rim cell: the result equals the input.
 
 flow_direction.  ESRI's codes, the neighbours (drow, dcol) in this fixed order: E 1 (0, +1), SE 2 (+1, +1), S 4 (+1, 0),
 SW 8 (+1, -1), W 16 (0, -1), NW 32 (-1, -1), N 64 (-1, 0), NE 128 (-1, +1).
@@ -12,6 +23,17 @@ SW 8 (+1, -1), W 16 (0, -1), NW 32 (-1, -1), N 64 (-1, 0), NE 128 (-1, +1).
      with no lower neighbour get 0;
   5. a NaN cell gives NaN.  The result is float32.
 float32 and float64 rasters are read in place; every other numeric dtype is cast to float64 on the host.
+
+flow_direction(resolve_flats=True).  code0 = the result above.  A cell is drained if it is a rim cell or code0 != 0; every other
+non-NaN cell is a flat cell.
+  1. d(c) = 0 at drained cells;
+  2. at a flat cell d(c) = 1 + min d(n) over the neighbours with z(n) == z(c), compared in the raster's dtype: the 8-connected
+     step count, through cells of equal elevation, to the nearest drained cell of that elevation; infinite without one;
+  3. a flat cell with finite d gets the code of the first neighbour, in the order above, with z(n) == z(c) and d(n) == d(c) - 1;
+  4. a flat cell with infinite d (a closed pit or flat of an unfilled DEM) keeps 0;
+  5. drained cells keep code0 (a rim cell with code 0 is an outlet); NaN cells stay NaN.
+Along a path z never rises and among equal z the count d falls strictly: no cycle.  On W = fill(z) every flat cell has a finite d,
+so every path of flow_direction(W, resolve_flats=True) ends in a rim cell.
 
 flow_accumulation, basins.  The input is a raster of such codes, staged as float32.
   1. a NaN cell is outside the graph: both results are NaN there;
@@ -48,6 +70,8 @@ TIMED = 1                               # XRS_FLOW_TIMED
 STATUS_WORDS = 80
 MAX_CELLS = 2 ** 32 - 2
 CODES = (0, 1, 2, 4, 8, 16, 32, 64, 128)
+TILE = 64                               # XRS_FILL_TILE: the tile edge of the fill / flat relaxer
+FILL_STATUS_WORDS, FILL_STATUS_ROUNDS = 256, 80     # XRS_FILL_STATUS_WORDS / XRS_FILL_STATUS_ROUNDS
 
 
 def _check_raster(data, what):
@@ -72,8 +96,61 @@ def cell_distances(agg):
     return float(cx), float(cy), float(dg)
 
 
+def relax_rounds(words):
+    """The per-round part of xrs_fill's / xrs_flow_flats' status words: rounds run, then for the first FILL_STATUS_ROUNDS of them
+    the cells that changed, the tiles launched and (with TIMED) the nanoseconds."""
+    kept = min(words[0], FILL_STATUS_ROUNDS)
+    return {"rounds": words[0], "tiles_launched": words[1], "changed": words[8:8 + kept],
+            "tiles": words[8 + FILL_STATUS_ROUNDS:8 + FILL_STATUS_ROUNDS + kept],
+            "ns": words[8 + 2 * FILL_STATUS_ROUNDS:8 + 2 * FILL_STATUS_ROUNDS + kept]}
+
+
+# ------------------------------------------------------------------ fill
+def fill_plane(src: DeviceArray, flags: int = 0, stream=None):
+    """xrs_fill on a resident float32 / float64 plane: (the filled plane, status words)."""
+    rows, cols = src.shape
+    out = DeviceArray((rows, cols), src.dtype)
+    status = (ctypes.c_int64 * FILL_STATUS_WORDS)()
+    if rows * cols:
+        work = workspace("fill", rows, cols)
+        _lib.call("xrs_fill", src.ptr, DTYPE_CODE[src.dtype], rows, cols, out.ptr, work.ptr, status, flags, stream)
+    return out, [int(w) for w in status]
+
+
+def _run_fill(data):
+    _lib.require_device()
+    stream = get_stream()
+    src, like_numpy = resident(data, stream, FLOAT_SUFFIX, np.float64)
+    out, _ = fill_plane(src, stream=stream)
+    settle(stream, like_numpy)                                           # the workspace goes back to the pool
+    return finish(out, like_numpy)
+
+
+@supports_dataset
+def fill(agg: DataArray, name: str = 'fill') -> DataArray:
+    """Depression fill: every cell raised to the level at which its water reaches the rim of the raster (a cell with a neighbour
+    outside the raster or NaN); NaN at NaN cells.  Every output value is an input value (the rule: module docstring).
+
+    agg: 2-D DataArray of elevations (or a Dataset: every variable on its own), NumPy- or DeviceArray-backed (the result's
+    backend).  Returns a DataArray of agg's dtype (float32 or float64; any other numeric dtype gives float64) with agg's coords,
+    dims and attrs."""
+    refuse_split_backends(agg, 'fill')
+    _check_raster(agg.data, 'fill')
+    return DataArray(_run_fill(agg.data), name=name, coords=agg.coords, dims=agg.dims, attrs=agg.attrs)
+
+
 # ------------------------------------------------------------------ flow_direction
-def _run_direction(data, cx, cy, dg):
+def resolve_flats_plane(src: DeviceArray, codes: DeviceArray, flags: int = 0, stream=None):
+    """xrs_flow_flats: the codes of xrs_flow_direction for the resident plane `src`, updated in place; the status words."""
+    rows, cols = src.shape
+    status = (ctypes.c_int64 * FILL_STATUS_WORDS)()
+    if rows * cols:
+        work = workspace("flow_flats", rows, cols)
+        _lib.call("xrs_flow_flats", src.ptr, DTYPE_CODE[src.dtype], rows, cols, codes.ptr, work.ptr, status, flags, stream)
+    return [int(w) for w in status]
+
+
+def _run_direction(data, cx, cy, dg, resolve_flats=False):
     _lib.require_device()
     stream = get_stream()
     src, like_numpy = resident(data, stream, FLOAT_SUFFIX, np.float64)
@@ -81,23 +158,26 @@ def _run_direction(data, cx, cy, dg):
     out = DeviceArray((rows, cols), np.float32)
     if rows * cols:
         _lib.call("xrs_flow_direction", src.ptr, DTYPE_CODE[src.dtype], rows, cols, cx, cy, dg, out.ptr, stream)
-        if src is not data:
-            settle(stream, like_numpy)                                   # the widened copy goes back to the pool
+        if resolve_flats:
+            resolve_flats_plane(src, out, stream=stream)
+        if src is not data or resolve_flats:
+            settle(stream, like_numpy)                                   # the widened copy and the workspace go back to the pool
     return finish(out, like_numpy)
 
 
 @supports_dataset
-def flow_direction(agg: DataArray, name: str = 'flow_direction') -> DataArray:
+def flow_direction(agg: DataArray, name: str = 'flow_direction', resolve_flats: bool = False) -> DataArray:
     """D8 flow direction: for every cell the ESRI code (E 1, SE 2, S 4, SW 8, W 16, NW 32, N 64, NE 128) of the neighbour with
     the steepest drop, 0 where no neighbour lies lower, NaN at NaN cells (the rule: module docstring).
 
     agg: 2-D DataArray of elevations (or a Dataset: every variable on its own), NumPy- or DeviceArray-backed (the result's
-    backend); the cell size comes from `attrs['res']` or the coordinates, as for `slope`.  Returns a float32 DataArray with
-    agg's coords, dims and attrs."""
+    backend); the cell size comes from `attrs['res']` or the coordinates, as for `slope`.  resolve_flats: give every cell of a
+    level area that has a drained cell the code of the neighbour one step nearer to it (on `fill(agg)` every path then ends at
+    the rim of the raster).  Returns a float32 DataArray with agg's coords, dims and attrs."""
     refuse_split_backends(agg, 'flow_direction')
     rows, cols = _check_raster(agg.data, 'flow_direction')
     cx, cy, dg = cell_distances(agg) if rows * cols else (1.0, 1.0, float(np.sqrt(2.0)))
-    out = _run_direction(agg.data, cx, cy, dg)
+    out = _run_direction(agg.data, cx, cy, dg, bool(resolve_flats))
     return DataArray(out, name=name, coords=agg.coords, dims=agg.dims, attrs=agg.attrs)
 
 
