@@ -12,6 +12,7 @@
 //   SEARCH   the same bins, many of them: lower_bound by bisection.
 // Every comparison is in float64, as Numba compares a float32 / integer cell with float64 bins.
 #include "xrs_common.h"
+#include "dtype_dispatch.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -592,18 +593,11 @@ int xrs_classify_to_f64(const void *in_dev, int dtype_code, double *out_dev, int
     if (!in_dev || !out_dev) return fail("xrs_classify_to_f64: null pointer");
     const dim3 g((unsigned)((n + 255) / 256)), b(256);
     hipStream_t s = as_stream(stream);
-    switch (dtype_code) {
-    case XRS_DT_I8: hipLaunchKernelGGL(to_f64_kernel<int8_t>, g, b, 0, s, (const int8_t *)in_dev, out_dev, n); break;
-    case XRS_DT_U8: hipLaunchKernelGGL(to_f64_kernel<uint8_t>, g, b, 0, s, (const uint8_t *)in_dev, out_dev, n); break;
-    case XRS_DT_I16: hipLaunchKernelGGL(to_f64_kernel<int16_t>, g, b, 0, s, (const int16_t *)in_dev, out_dev, n); break;
-    case XRS_DT_U16: hipLaunchKernelGGL(to_f64_kernel<uint16_t>, g, b, 0, s, (const uint16_t *)in_dev, out_dev, n); break;
-    case XRS_DT_I32: hipLaunchKernelGGL(to_f64_kernel<int32_t>, g, b, 0, s, (const int32_t *)in_dev, out_dev, n); break;
-    case XRS_DT_U32: hipLaunchKernelGGL(to_f64_kernel<uint32_t>, g, b, 0, s, (const uint32_t *)in_dev, out_dev, n); break;
-    case XRS_DT_I64: hipLaunchKernelGGL(to_f64_kernel<int64_t>, g, b, 0, s, (const int64_t *)in_dev, out_dev, n); break;
-    case XRS_DT_U64: hipLaunchKernelGGL(to_f64_kernel<uint64_t>, g, b, 0, s, (const uint64_t *)in_dev, out_dev, n); break;
-    case XRS_DT_F32: hipLaunchKernelGGL(to_f64_kernel<float>, g, b, 0, s, (const float *)in_dev, out_dev, n); break;
-    default: return fail("xrs_classify_to_f64: unsupported dtype code %d", dtype_code);
-    }
+    const bool known = with_dtype<DT_NO_F64>(dtype_code, [&](auto t) {
+        using T = dtype_of<decltype(t)>;
+        hipLaunchKernelGGL(to_f64_kernel<T>, g, b, 0, s, (const T *)in_dev, out_dev, n);
+    });
+    if (!known) return fail("xrs_classify_to_f64: unsupported dtype code %d", dtype_code);
     XRS_LAUNCH_CHECK();
     return 0;
 }

@@ -6,6 +6,7 @@
 // Both are streaming byte work: every cell is read once, 12 B in / 4 B out for the composite, the raster's own
 // dtype in / 16 B out for the bounding box.
 #include "xrs_common.h"
+#include "dtype_dispatch.h"
 
 #include <climits>
 #include <cmath>
@@ -220,19 +221,10 @@ int xrs_true_color_u8(const float *red_dev, const float *green_dev, const float 
     g = g > 16384 ? 16384 : g;
     const dim3 grid((unsigned)g), block(256);
     hipStream_t s = as_stream(stream);
-    switch (red_raw_dtype) {
-        case XRS_DT_I8: hipLaunchKernelGGL(true_color_kernel<int8_t>, grid, block, 0, s, a); break;
-        case XRS_DT_U8: hipLaunchKernelGGL(true_color_kernel<uint8_t>, grid, block, 0, s, a); break;
-        case XRS_DT_I16: hipLaunchKernelGGL(true_color_kernel<int16_t>, grid, block, 0, s, a); break;
-        case XRS_DT_U16: hipLaunchKernelGGL(true_color_kernel<uint16_t>, grid, block, 0, s, a); break;
-        case XRS_DT_I32: hipLaunchKernelGGL(true_color_kernel<int32_t>, grid, block, 0, s, a); break;
-        case XRS_DT_U32: hipLaunchKernelGGL(true_color_kernel<uint32_t>, grid, block, 0, s, a); break;
-        case XRS_DT_I64: hipLaunchKernelGGL(true_color_kernel<int64_t>, grid, block, 0, s, a); break;
-        case XRS_DT_U64: hipLaunchKernelGGL(true_color_kernel<uint64_t>, grid, block, 0, s, a); break;
-        case XRS_DT_F64: hipLaunchKernelGGL(true_color_kernel<double>, grid, block, 0, s, a); break;
-        case XRS_DT_F32: hipLaunchKernelGGL(true_color_kernel<float>, grid, block, 0, s, a); break;
-        default: return fail("xrs_true_color_u8: unknown dtype code %d", red_raw_dtype);
-    }
+    const bool known = with_dtype_f32_last(red_raw_dtype, [&](auto t) {
+        hipLaunchKernelGGL(true_color_kernel<dtype_of<decltype(t)>>, grid, block, 0, s, a);
+    });
+    if (!known) return fail("xrs_true_color_u8: unknown dtype code %d", red_raw_dtype);
     XRS_LAUNCH_CHECK();
     return 0;
 }
@@ -253,19 +245,10 @@ int xrs_match_bbox(const void *data_dev, int dtype, int64_t rows, int64_t cols, 
         a.box = box4_dev;
         long g = rows < 4096 ? rows : 4096;
         const dim3 grid((unsigned)g), block(256);
-        switch (dtype) {
-            case XRS_DT_I8: hipLaunchKernelGGL(box_kernel<int8_t>, grid, block, 0, s, a); break;
-            case XRS_DT_U8: hipLaunchKernelGGL(box_kernel<uint8_t>, grid, block, 0, s, a); break;
-            case XRS_DT_I16: hipLaunchKernelGGL(box_kernel<int16_t>, grid, block, 0, s, a); break;
-            case XRS_DT_U16: hipLaunchKernelGGL(box_kernel<uint16_t>, grid, block, 0, s, a); break;
-            case XRS_DT_I32: hipLaunchKernelGGL(box_kernel<int32_t>, grid, block, 0, s, a); break;
-            case XRS_DT_U32: hipLaunchKernelGGL(box_kernel<uint32_t>, grid, block, 0, s, a); break;
-            case XRS_DT_I64: hipLaunchKernelGGL(box_kernel<int64_t>, grid, block, 0, s, a); break;
-            case XRS_DT_U64: hipLaunchKernelGGL(box_kernel<uint64_t>, grid, block, 0, s, a); break;
-            case XRS_DT_F64: hipLaunchKernelGGL(box_kernel<double>, grid, block, 0, s, a); break;
-            case XRS_DT_F32: hipLaunchKernelGGL(box_kernel<float>, grid, block, 0, s, a); break;
-            default: return fail("xrs_match_bbox: unknown dtype code %d", dtype);
-        }
+        const bool known = with_dtype_f32_last(dtype, [&](auto t) {
+            hipLaunchKernelGGL(box_kernel<dtype_of<decltype(t)>>, grid, block, 0, s, a);
+        });
+        if (!known) return fail("xrs_match_bbox: unknown dtype code %d", dtype);
     }
     XRS_LAUNCH_CHECK();
     return 0;

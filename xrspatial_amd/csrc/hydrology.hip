@@ -18,6 +18,7 @@
 //               loop depends on the data.
 //   finish      uint32 -> float64, NaN at NaN cells.
 #include "xrs_common.h"
+#include "dtype_dispatch.h"
 
 #include <chrono>
 #include <cmath>
@@ -301,7 +302,7 @@ extern "C" {
 int xrs_flow_direction(const void *data_dev, int dtype, int64_t rows, int64_t cols, double cellsize_x, double cellsize_y, double diag,
                        float *out_dev, void *stream) {
     if (rows < 0 || cols < 0) return fail("xrs_flow_direction: negative shape");
-    if (dtype != XRS_DT_F32 && dtype != XRS_DT_F64) return fail("xrs_flow_direction: unsupported dtype code %d (float32 or float64)", dtype);
+    if (!dtype_in(DT_FLOATS, dtype)) return fail("xrs_flow_direction: unsupported dtype code %d (float32 or float64)", dtype);
     if (!(cellsize_x > 0.0) || !(cellsize_y > 0.0) || !(diag > 0.0) || std::isinf(cellsize_x) || std::isinf(cellsize_y) || std::isinf(diag))
         return fail("xrs_flow_direction: cell sizes must be positive and finite (%g, %g, diagonal %g)", cellsize_x, cellsize_y, diag);
     if (rows == 0 || cols == 0) return 0;
@@ -311,12 +312,11 @@ int xrs_flow_direction(const void *data_dev, int dtype, int64_t rows, int64_t co
     if (!data_dev || !out_dev) return fail("xrs_flow_direction: null pointer");
     hipStream_t s = as_stream(stream);
     const dim3 grid((unsigned)(bands * spans));
-    if (dtype == XRS_DT_F32)
-        hipLaunchKernelGGL((flow_direction_kernel<float>), grid, dim3(SPAN), 0, s, static_cast<const float *>(data_dev), (long)rows,
+    with_dtype<DT_FLOATS>(dtype, [&](auto t) {                    // (the code was checked above)
+        using T = dtype_of<decltype(t)>;
+        hipLaunchKernelGGL((flow_direction_kernel<T>), grid, dim3(SPAN), 0, s, static_cast<const T *>(data_dev), (long)rows,
                            (long)cols, (unsigned)spans, cellsize_x, cellsize_y, diag, out_dev);
-    else
-        hipLaunchKernelGGL((flow_direction_kernel<double>), grid, dim3(SPAN), 0, s, static_cast<const double *>(data_dev), (long)rows,
-                           (long)cols, (unsigned)spans, cellsize_x, cellsize_y, diag, out_dev);
+    });
     XRS_LAUNCH_CHECK();
     return 0;
 }

@@ -24,6 +24,7 @@
 //            and stops at the first round in which nothing fell; after rows * cols + 1 rounds it returns an error.
 //            No loop depends on the data without a bound, nothing waits on another block.
 #include "xrs_common.h"
+#include "dtype_dispatch.h"
 
 #include <chrono>
 #include <cmath>
@@ -360,7 +361,7 @@ int check_call(const char *what, const void *z, int dtype, int64_t rows, int64_t
                int flags, bool *empty) {
     *empty = true;
     if (rows < 0 || cols < 0) return fail("%s: negative shape", what);
-    if (dtype != XRS_DT_F32 && dtype != XRS_DT_F64) return fail("%s: unsupported dtype code %d (float32 or float64)", what, dtype);
+    if (!dtype_in(DT_FLOATS, dtype)) return fail("%s: unsupported dtype code %d (float32 or float64)", what, dtype);
     if (flags & ~XRS_FILL_TIMED) return fail("%s: unknown flags %d", what, flags);
     if (!status) return fail("%s: null status pointer", what);
     for (int w = 0; w < XRS_FILL_STATUS_WORDS; ++w) status[w] = 0;
@@ -425,11 +426,13 @@ int xrs_fill(const void *z_dev, int dtype, int64_t rows, int64_t cols, void *out
     if (int rc = check_call("xrs_fill", z_dev, dtype, rows, cols, out_dev, work_dev, status_host, flags, &empty)) return rc;
     if (empty) return 0;
     const bool timed = flags & XRS_FILL_TIMED;
-    if (dtype == XRS_DT_F32)
-        return fill_typed(static_cast<const float *>(z_dev), (long)rows, (long)cols, static_cast<float *>(out_dev), work_dev, status_host, timed,
-                          as_stream(stream));
-    return fill_typed(static_cast<const double *>(z_dev), (long)rows, (long)cols, static_cast<double *>(out_dev), work_dev, status_host, timed,
-                      as_stream(stream));
+    int rc = 0;
+    with_dtype<DT_FLOATS>(dtype, [&](auto t) {                    // check_call refused every other code
+        using T = dtype_of<decltype(t)>;
+        rc = fill_typed(static_cast<const T *>(z_dev), (long)rows, (long)cols, static_cast<T *>(out_dev), work_dev, status_host, timed,
+                        as_stream(stream));
+    });
+    return rc;
 }
 
 int xrs_flow_flats_workspace_size(int64_t rows, int64_t cols, uint64_t *bytes_out) {
@@ -442,9 +445,12 @@ int xrs_flow_flats(const void *z_dev, int dtype, int64_t rows, int64_t cols, flo
     if (int rc = check_call("xrs_flow_flats", z_dev, dtype, rows, cols, code_dev, work_dev, status_host, flags, &empty)) return rc;
     if (empty) return 0;
     const bool timed = flags & XRS_FILL_TIMED;
-    if (dtype == XRS_DT_F32)
-        return flats_typed(static_cast<const float *>(z_dev), (long)rows, (long)cols, code_dev, work_dev, status_host, timed, as_stream(stream));
-    return flats_typed(static_cast<const double *>(z_dev), (long)rows, (long)cols, code_dev, work_dev, status_host, timed, as_stream(stream));
+    int rc = 0;
+    with_dtype<DT_FLOATS>(dtype, [&](auto t) {                    // check_call refused every other code
+        rc = flats_typed(static_cast<const dtype_of<decltype(t)> *>(z_dev), (long)rows, (long)cols, code_dev, work_dev, status_host, timed,
+                         as_stream(stream));
+    });
+    return rc;
 }
 
 }  // extern "C"

@@ -16,6 +16,7 @@
 //              classes.  Equal tuples never change their relative order, so the first cell of a final run is the tuple's
 //              first occurrence in row-major order; sorting the classes by that cell gives the reference's ids.
 #include "xrs_common.h"
+#include "dtype_dispatch.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -52,31 +53,17 @@ template <typename W> __device__ __forceinline__ W largest() {
     else return (W)0x7fffffffffffffffll;
 }
 
-// one cell of a plane, widened
-template <typename W> __device__ __forceinline__ W ld(const void *p, int dt, long i) {
-    switch (dt) {
-    case XRS_DT_I8: return (W) static_cast<const int8_t *>(p)[i];
-    case XRS_DT_U8: return (W) static_cast<const uint8_t *>(p)[i];
-    case XRS_DT_I16: return (W) static_cast<const int16_t *>(p)[i];
-    case XRS_DT_U16: return (W) static_cast<const uint16_t *>(p)[i];
-    case XRS_DT_I32: return (W) static_cast<const int32_t *>(p)[i];
-    case XRS_DT_U32: return (W) static_cast<const uint32_t *>(p)[i];
-    case XRS_DT_I64: return (W) static_cast<const int64_t *>(p)[i];
-    case XRS_DT_F64: return (W) static_cast<const double *>(p)[i];
-    default: return (W) static_cast<const float *>(p)[i];
-    }
-}
-
+// One cell of a plane, widened, is load_as<W, DT_NO_U64> (dtype_dispatch.h).
 // cells i and i + 1 of a plane (i even): one 8- or 16-byte load for the 4- and 8-byte dtypes
 template <typename W> __device__ __forceinline__ void ld2(const void *p, int dt, long i, bool two, W &a, W &b) {
-    if (!two) { a = ld<W>(p, dt, i); b = a; return; }
+    if (!two) { a = load_as<W, DT_NO_U64>(p, dt, i); b = a; return; }
     switch (dt) {
     case XRS_DT_F32: { const f2u v = *reinterpret_cast<const f2u *>(static_cast<const float *>(p) + i); a = (W)v.x; b = (W)v.y; return; }
     case XRS_DT_F64: { const xrs_d2u v = *reinterpret_cast<const xrs_d2u *>(static_cast<const double *>(p) + i); a = (W)v.x; b = (W)v.y; return; }
     case XRS_DT_I32: { const i2u v = *reinterpret_cast<const i2u *>(static_cast<const int32_t *>(p) + i); a = (W)v.x; b = (W)v.y; return; }
     case XRS_DT_U32: { const u2u v = *reinterpret_cast<const u2u *>(static_cast<const uint32_t *>(p) + i); a = (W)v.x; b = (W)v.y; return; }
     case XRS_DT_I64: { const l2u v = *reinterpret_cast<const l2u *>(static_cast<const int64_t *>(p) + i); a = (W)v.x; b = (W)v.y; return; }
-    default: a = ld<W>(p, dt, i); b = ld<W>(p, dt, i + 1); return;
+    default: a = load_as<W, DT_NO_U64>(p, dt, i); b = load_as<W, DT_NO_U64>(p, dt, i + 1); return;
     }
 }
 
@@ -273,7 +260,7 @@ template <typename W, int N> struct Sorted {
         for (int j = 0; j < N; ++j) {
             v[j] = largest<W>();
             if (j < np) {
-                v[j] = ld<W>(args.p[j], args.dt[j], i);
+                v[j] = load_as<W, DT_NO_U64>(args.p[j], args.dt[j], i);
                 bad |= is_nan(v[j]);
             }
         }
@@ -289,7 +276,7 @@ template <typename W> struct Sorted<W, 0> {
         col = lds + threadIdx.x;
         bool bad = false;
         for (int j = 0; j < np; ++j) {
-            const W x = ld<W>(args.p[j], args.dt[j], i);
+            const W x = load_as<W, DT_NO_U64>(args.p[j], args.dt[j], i);
             bad |= is_nan(x);
             int k = j;
             while (k > 0) {
@@ -317,7 +304,7 @@ __global__ void __launch_bounds__(N ? 256 : LDS_THREADS) local_values_kernel(con
         const int h = np >> 1;
         if (!bad) r = (np & 1) ? (double)s.at(h) : ((double)s.at(h - 1) + (double)s.at(h)) / 2.0;
     } else {
-        i64 k = ref_minus_one(ld<i64>(ref, ref_dt, i), ref_dt);
+        i64 k = ref_minus_one(load_as<i64, DT_NO_U64>(ref, ref_dt, i), ref_dt);
         if constexpr (OP == XRS_LOCAL_RANK) {
             if (k < 0) k += np;                                // Python's wrap; below it the reference raises IndexError: NaN here
             if (!bad && k >= 0 && k < np) r = (double)s.at((int)k);
@@ -358,16 +345,7 @@ __global__ void __launch_bounds__(N ? 256 : LDS_THREADS) local_values_kernel(con
     st_stream(out + i, r);
 }
 
-inline bool dtype_ok(int dt) { return dt >= XRS_DT_I8 && dt <= XRS_DT_F32 && dt != XRS_DT_U64; }
-inline bool dtype_float(int dt) { return dt == XRS_DT_F32 || dt == XRS_DT_F64; }
-inline int dtype_size(int dt) {
-    switch (dt) {
-    case XRS_DT_I8: case XRS_DT_U8: return 1;
-    case XRS_DT_I16: case XRS_DT_U16: return 2;
-    case XRS_DT_I32: case XRS_DT_U32: case XRS_DT_F32: return 4;
-    default: return 8;
-    }
-}
+inline bool dtype_float(int dt) { return dtype_in(DT_FLOATS, dt); }
 
 int fill_args(const char *who, const void *const *planes, const int *dtypes, int n_planes, LocalArgs &args, bool &any_float) {
     if (!planes || !dtypes) return fail("%s: null pointer", who);
@@ -376,7 +354,7 @@ int fill_args(const char *who, const void *const *planes, const int *dtypes, int
     any_float = false;
     for (int j = 0; j < n_planes; ++j) {
         if (!planes[j]) return fail("%s: null pointer (plane %d)", who, j);
-        if (!dtype_ok(dtypes[j])) return fail("%s: plane %d has unsupported dtype code %d", who, j, dtypes[j]);
+        if (!dtype_in(DT_NO_U64, dtypes[j])) return fail("%s: plane %d has unsupported dtype code %d", who, j, dtypes[j]);
         args.p[j] = planes[j];
         args.dt[j] = (unsigned char)dtypes[j];
         any_float |= dtype_float(dtypes[j]);
@@ -497,8 +475,8 @@ __global__ void __launch_bounds__(256) local_gather_kernel(const LocalArgs args,
         const int dt = args.dt[j];
         u64 bits = 0;
         if ((long)c < n) {
-            if (dt == XRS_DT_F32 || dt == XRS_DT_F64) bits = (u64)__double_as_longlong(ld<double>(args.p[j], dt, c));
-            else bits = (u64)ld<i64>(args.p[j], dt, c);
+            if (dt == XRS_DT_F32 || dt == XRS_DT_F64) bits = (u64)__double_as_longlong(load_as<double, DT_NO_U64>(args.p[j], dt, c));
+            else bits = (u64)load_as<i64, DT_NO_U64>(args.p[j], dt, c);
         }
         out[t * np + j] = bits;
     }
@@ -549,7 +527,7 @@ int xrs_local_cells(int op, const void *const *planes, const int *dtypes, int n_
                            op == XRS_LOCAL_POPULARITY;
     if (needs_ref) {
         if (!ref_dev) return fail("xrs_local_cells: null pointer (ref)");
-        if (!dtype_ok(ref_dtype)) return fail("xrs_local_cells: ref has unsupported dtype code %d", ref_dtype);
+        if (!dtype_in(DT_NO_U64, ref_dtype)) return fail("xrs_local_cells: ref has unsupported dtype code %d", ref_dtype);
         if ((op == XRS_LOCAL_RANK || op == XRS_LOCAL_POPULARITY) && dtype_float(ref_dtype))
             return fail("xrs_local_cells: rank and popularity need an integer ref");
         any_float |= dtype_float(ref_dtype);
@@ -640,7 +618,7 @@ int xrs_local_combine(const void *const *planes, const int *dtypes, int n_planes
         XRS_LAUNCH_CHECK();
         hipcub::DoubleBuffer<u64> dk(key[0], key[1]);
         size_t cb = pl.cub_bytes;
-        XRS_HIP(hipcub::DeviceRadixSort::SortPairs(cub, cb, dk, di, (int)n, 0, 8 * dtype_size(args.dt[j]), s));
+        XRS_HIP(hipcub::DeviceRadixSort::SortPairs(cub, cb, dk, di, (int)n, 0, 8 * dtype_bytes(args.dt[j]), s));
         unsigned *ck[2] = {reinterpret_cast<unsigned *>(key[0]), reinterpret_cast<unsigned *>(key[1])};     // (the value keys are done with)
         hipLaunchKernelGGL(combine_class_key_kernel, grid, block, 0, s, cls, di.Current(), (long)n, ck[0]);
         XRS_LAUNCH_CHECK();

@@ -31,6 +31,7 @@
 //            rows * cols + 2 passes, and beyond that the call fails instead of looping.
 // No floating point but the walk's sum, and that is an add of literals: nothing here can be contracted.
 #include "xrs_common.h"
+#include "dtype_dispatch.h"
 #include "value_match.h"
 #include "wave_reduce.h"
 
@@ -332,7 +333,7 @@ int xrs_astar(const void *data_dev, int dtype, int64_t rows, int64_t cols, int64
               void *work_dev, double *out_dev, int64_t *status_host, void *stream) {
     if (rows < 0 || cols < 0) return fail("xrs_astar: negative shape");
     if (connectivity != 4 && connectivity != 8) return fail("xrs_astar: connectivity %d is neither 4 nor 8", connectivity);
-    if (dtype < XRS_DT_I8 || dtype > XRS_DT_F32) return fail("xrs_astar: unsupported dtype code %d", dtype);
+    if (!dtype_bytes(dtype)) return fail("xrs_astar: unsupported dtype code %d", dtype);
     if (n_barriers < 0) return fail("xrs_astar: negative number of barrier values");
     if (barriers_kind != XRS_PROX_VALUES_F64 && barriers_kind != XRS_PROX_VALUES_I64 && barriers_kind != XRS_PROX_VALUES_U64)
         return fail("xrs_astar: unknown kind of barrier values %d", barriers_kind);
@@ -358,15 +359,9 @@ int xrs_astar(const void *data_dev, int dtype, int64_t rows, int64_t cols, int64
     long long *st = (long long *)(base + pl.status_off), *partial = (long long *)(base + pl.partial_off);
     XRS_HIP(hipMemsetAsync(base + pl.dirty_off[0], 0, pl.partial_off - pl.dirty_off[0], s));   // both dirty arrays, changed, status
 
-#define XRS_ASTAR_INIT(T) launch_init<T>(data_dev, n, barriers_dev, barriers_kind, n_barriers, field, out_dev, s); break
-    switch (dtype) {
-    case XRS_DT_I8: XRS_ASTAR_INIT(int8_t); case XRS_DT_U8: XRS_ASTAR_INIT(uint8_t);
-    case XRS_DT_I16: XRS_ASTAR_INIT(int16_t); case XRS_DT_U16: XRS_ASTAR_INIT(uint16_t);
-    case XRS_DT_I32: XRS_ASTAR_INIT(int32_t); case XRS_DT_U32: XRS_ASTAR_INIT(uint32_t);
-    case XRS_DT_I64: XRS_ASTAR_INIT(int64_t); case XRS_DT_U64: XRS_ASTAR_INIT(uint64_t);
-    case XRS_DT_F64: XRS_ASTAR_INIT(double); default: XRS_ASTAR_INIT(float);
-    }
-#undef XRS_ASTAR_INIT
+    with_dtype_f32_last(dtype, [&](auto t) {   // (the code was checked above)
+        launch_init<dtype_of<decltype(t)>>(data_dev, n, barriers_dev, barriers_kind, n_barriers, field, out_dev, s);
+    });
     XRS_LAUNCH_CHECK();
     int n_partial = 0;
     if (snap_flags & (XRS_ASTAR_SNAP_START | XRS_ASTAR_SNAP_GOAL)) {

@@ -27,6 +27,7 @@
 // Every loop is bounded, no workgroup waits for another (the only cross-workgroup traffic is the lock-free union of
 // merge_kernel and one atomicAdd per ring), and every store is an ordinary vector store.
 #include "xrs_common.h"
+#include "dtype_dispatch.h"
 #include "union_find.h"
 
 #include <hipcub/hipcub.hpp>
@@ -549,26 +550,6 @@ template <typename T> int mask_impl(const T *m, uint64_t n, uint8_t *out, hipStr
     return 0;
 }
 
-#define XRS_POLY_DISPATCH(CODE, CALL)                                                                                    \
-    switch (CODE) {                                                                                                      \
-    case XRS_DT_I8: CALL(int8_t); case XRS_DT_U8: CALL(uint8_t);                                                         \
-    case XRS_DT_I16: CALL(int16_t); case XRS_DT_U16: CALL(uint16_t);                                                     \
-    case XRS_DT_I32: CALL(int32_t); case XRS_DT_U32: CALL(uint32_t);                                                     \
-    case XRS_DT_I64: CALL(int64_t); case XRS_DT_U64: CALL(uint64_t);                                                     \
-    case XRS_DT_F32: CALL(float); case XRS_DT_F64: CALL(double);                                                         \
-    default: return fail("unsupported dtype code %d", CODE);                                                             \
-    }
-
-int dtype_bytes(int dtype) {
-    switch (dtype) {
-    case XRS_DT_I8: case XRS_DT_U8: return 1;
-    case XRS_DT_I16: case XRS_DT_U16: return 2;
-    case XRS_DT_I32: case XRS_DT_U32: case XRS_DT_F32: return 4;
-    case XRS_DT_I64: case XRS_DT_U64: case XRS_DT_F64: return 8;
-    default: return 0;
-    }
-}
-
 }  // namespace
 
 extern "C" {
@@ -595,20 +576,17 @@ int xrs_polygonize_census(const void *data_dev, int dtype, const void *mask_dev,
     hipStream_t s = as_stream(stream);
     const Plan p = plan(rows, cols);
     uint8_t *mask = nullptr;
+    int rc = 0;                                                   // (both codes were checked above)
     if (mask_dev) {
         mask = (uint8_t *)work_dev + p.mask_off;
-#define XRS_POLY_MASK(T)                                                                                                 \
-    {                                                                                                                    \
-        if (int rc = mask_impl<T>((const T *)mask_dev, p.n, mask, s)) return rc;                                         \
-        break;                                                                                                           \
-    }
-        XRS_POLY_DISPATCH(mask_dtype, XRS_POLY_MASK)
-#undef XRS_POLY_MASK
+        with_dtype(mask_dtype, [&](auto t) { rc = mask_impl((const dtype_of<decltype(t)> *)mask_dev, p.n, mask, s); });
+        if (rc) return rc;
     }
     const int n8 = connectivity == 8;
-#define XRS_POLY_CENSUS(T) return census_impl<T>((const T *)data_dev, mask, rows, cols, n8, work_dev, n_regions, n_states, s)
-    XRS_POLY_DISPATCH(dtype, XRS_POLY_CENSUS)
-#undef XRS_POLY_CENSUS
+    with_dtype(dtype, [&](auto t) {
+        rc = census_impl((const dtype_of<decltype(t)> *)data_dev, mask, rows, cols, n8, work_dev, n_regions, n_states, s);
+    });
+    return rc;
 }
 
 int xrs_polygonize_rings(int64_t rows, int64_t cols, const void *work_dev, void *rings_dev, uint64_t n_states,

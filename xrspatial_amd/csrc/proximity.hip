@@ -28,6 +28,7 @@
 // Workspace (ABI, include/xrs_hip.h): left | right | flag | list | count, each part rounded up to 256 bytes (plan()).
 // Contraction is off for the whole file: dx * dx + dy * dy must round as the reference's.
 #include "xrs_common.h"
+#include "dtype_dispatch.h"
 #include "value_match.h"
 #include "wave_reduce.h"
 
@@ -154,21 +155,6 @@ struct Search {
     int mode;
     float *out;                                  // MODE_ALL: three planes
 };
-
-__device__ __forceinline__ float cell_as_f32(const void *data, int dtype, long idx) {
-    switch (dtype) {
-    case XRS_DT_I8: return (float)static_cast<const int8_t *>(data)[idx];
-    case XRS_DT_U8: return (float)static_cast<const uint8_t *>(data)[idx];
-    case XRS_DT_I16: return (float)static_cast<const int16_t *>(data)[idx];
-    case XRS_DT_U16: return (float)static_cast<const uint16_t *>(data)[idx];
-    case XRS_DT_I32: return (float)static_cast<const int32_t *>(data)[idx];
-    case XRS_DT_U32: return (float)static_cast<const uint32_t *>(data)[idx];
-    case XRS_DT_I64: return (float)static_cast<const int64_t *>(data)[idx];
-    case XRS_DT_U64: return (float)static_cast<const uint64_t *>(data)[idx];
-    case XRS_DT_F64: return (float)static_cast<const double *>(data)[idx];
-    default: return static_cast<const float *>(data)[idx];
-    }
-}
 
 // `_calc_direction(x2, xs[c], y2, ys[r])` of a target that is not the cell itself
 __device__ __forceinline__ float compass(double x, double y) {
@@ -315,7 +301,7 @@ __global__ void __launch_bounds__(SPAN) proximity_search_kernel(const Search p) 
     float prox = nan_f32(), alloc = nan_f32(), dir = nan_f32();
     if (kept) {
         prox = (float)sqrt((double)s);
-        if (p.mode == MODE_ALLOCATION || p.mode == MODE_ALL) alloc = cell_as_f32(p.data, p.dtype, (long)best_r * p.cols + best_c);
+        if (p.mode == MODE_ALLOCATION || p.mode == MODE_ALL) alloc = load_as<float>(p.data, p.dtype, (long)best_r * p.cols + best_c);
         if (p.mode == MODE_DIRECTION || p.mode == MODE_ALL)
             dir = (best_r == i && best_c == j) ? 0.0f : compass(p.xs[best_c] - x2, p.ys[best_r] - y2);
     }
@@ -353,7 +339,7 @@ int xrs_proximity(const void *data_dev, int dtype, int64_t rows, int64_t cols, c
     if (mode & ~(3 | XRS_PROX_SCAN_ONLY | XRS_PROX_SEARCH_ONLY) || !(do_scan || do_search))
         return fail("xrs_proximity: unknown mode %d", mode);
     if (metric != EUCLIDEAN && metric != GREAT_CIRCLE && metric != MANHATTAN) return fail("xrs_proximity: unknown metric %d", metric);
-    if (dtype < XRS_DT_I8 || dtype > XRS_DT_F32) return fail("xrs_proximity: unsupported dtype code %d", dtype);
+    if (!dtype_bytes(dtype)) return fail("xrs_proximity: unsupported dtype code %d", dtype);
     if (n_values < 0) return fail("xrs_proximity: negative number of target values");
     if (values_kind != XRS_PROX_VALUES_F64 && values_kind != XRS_PROX_VALUES_I64 && values_kind != XRS_PROX_VALUES_U64)
         return fail("xrs_proximity: unknown kind of target values %d", values_kind);
@@ -374,15 +360,9 @@ int xrs_proximity(const void *data_dev, int dtype, int64_t rows, int64_t cols, c
     int *left = (int *)(base + pl.left_off), *right = (int *)(base + pl.right_off), *flag = (int *)(base + pl.flag_off);
     int *list = (int *)(base + pl.list_off), *count = (int *)(base + pl.count_off);
     if (do_scan) {
-#define XRS_PROX_SCAN(T) launch_scan<T>(data_dev, rows, cols, values_dev, values_kind, n_values, left, right, flag, s); break
-        switch (dtype) {
-        case XRS_DT_I8: XRS_PROX_SCAN(int8_t); case XRS_DT_U8: XRS_PROX_SCAN(uint8_t);
-        case XRS_DT_I16: XRS_PROX_SCAN(int16_t); case XRS_DT_U16: XRS_PROX_SCAN(uint16_t);
-        case XRS_DT_I32: XRS_PROX_SCAN(int32_t); case XRS_DT_U32: XRS_PROX_SCAN(uint32_t);
-        case XRS_DT_I64: XRS_PROX_SCAN(int64_t); case XRS_DT_U64: XRS_PROX_SCAN(uint64_t);
-        case XRS_DT_F64: XRS_PROX_SCAN(double); default: XRS_PROX_SCAN(float);
-        }
-#undef XRS_PROX_SCAN
+        with_dtype_f32_last(dtype, [&](auto t) {   // (the code was checked above)
+            launch_scan<dtype_of<decltype(t)>>(data_dev, rows, cols, values_dev, values_kind, n_values, left, right, flag, s);
+        });
         XRS_LAUNCH_CHECK();
         hipLaunchKernelGGL(proximity_rows_kernel, dim3(1), dim3(SPAN), 0, s, flag, (long)rows, list, count);
         XRS_LAUNCH_CHECK();

@@ -17,6 +17,7 @@
 //                 parent[] with device-scope CAS (why no flag, fence or grid barrier is needed);
 //   label_kernel  a new launch: root of every cell, label = prefix count up to the root, converted to T; NaN passes.
 #include "xrs_common.h"
+#include "dtype_dispatch.h"
 #include "union_find.h"
 
 #include <hipcub/hipcub.hpp>
@@ -277,7 +278,7 @@ int check_args(const char *fn, const void *data_dev, int dtype, int64_t rows, in
         return fail("%s: %lld x %lld cells exceed the 32-bit cell index (at most 2^32 - 1 cells)", fn, (long long)rows,
                     (long long)cols);
     if (neighborhood != 4 && neighborhood != 8) return fail("%s: neighborhood must be 4 or 8, got %d", fn, neighborhood);
-    if (dtype < XRS_DT_I8 || dtype > XRS_DT_F32) return fail("%s: unsupported dtype code %d", fn, dtype);
+    if (!dtype_bytes(dtype)) return fail("%s: unsupported dtype code %d", fn, dtype);
     if (rows * cols > 0 && (!data_dev || !work_dev)) return fail("%s: null pointer", fn);
     return 0;
 }
@@ -325,16 +326,6 @@ int label_impl(const T *in, T *out, int64_t rows, int64_t cols, int n8, void *wo
     return 0;
 }
 
-#define XRS_REGIONS_DISPATCH(CALL)                                                                                       \
-    switch (dtype) {                                                                                                     \
-    case XRS_DT_I8: CALL(int8_t); case XRS_DT_U8: CALL(uint8_t);                                                         \
-    case XRS_DT_I16: CALL(int16_t); case XRS_DT_U16: CALL(uint16_t);                                                     \
-    case XRS_DT_I32: CALL(int32_t); case XRS_DT_U32: CALL(uint32_t);                                                     \
-    case XRS_DT_I64: CALL(int64_t); case XRS_DT_U64: CALL(uint64_t);                                                     \
-    case XRS_DT_F32: CALL(float); case XRS_DT_F64: CALL(double);                                                         \
-    default: return fail("unsupported dtype code %d", dtype);                                                            \
-    }
-
 }  // namespace
 
 extern "C" {
@@ -352,9 +343,12 @@ int xrs_regions_link(const void *data_dev, int dtype, int64_t rows, int64_t cols
     if (rows * cols == 0) return 0;
     hipStream_t s = as_stream(stream);
     const int n8 = neighborhood == 8;
-#define XRS_REGIONS_LINK(T) return link_impl<T>((const T *)data_dev, rows, cols, n8, work_dev, n_new, s)
-    XRS_REGIONS_DISPATCH(XRS_REGIONS_LINK)
-#undef XRS_REGIONS_LINK
+    int rc = 0;
+    with_dtype(dtype, [&](auto t) {                               // check_args refused every other code
+        using T = dtype_of<decltype(t)>;
+        rc = link_impl<T>((const T *)data_dev, rows, cols, n8, work_dev, n_new, s);
+    });
+    return rc;
 }
 
 int xrs_regions_label(const void *data_dev, int dtype, int64_t rows, int64_t cols, int neighborhood, void *work_dev,
@@ -364,9 +358,12 @@ int xrs_regions_label(const void *data_dev, int dtype, int64_t rows, int64_t col
     if (!out_dev) return fail("xrs_regions_label: null pointer");
     hipStream_t s = as_stream(stream);
     const int n8 = neighborhood == 8;
-#define XRS_REGIONS_LABEL(T) return label_impl<T>((const T *)data_dev, (T *)out_dev, rows, cols, n8, work_dev, s)
-    XRS_REGIONS_DISPATCH(XRS_REGIONS_LABEL)
-#undef XRS_REGIONS_LABEL
+    int rc = 0;
+    with_dtype(dtype, [&](auto t) {                               // check_args refused every other code
+        using T = dtype_of<decltype(t)>;
+        rc = label_impl<T>((const T *)data_dev, (T *)out_dev, rows, cols, n8, work_dev, s);
+    });
+    return rc;
 }
 
 }  // extern "C"

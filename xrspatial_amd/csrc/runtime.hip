@@ -1,5 +1,6 @@
 // Runtime entry points: devices, memory, streams, events.  (include/xrs_hip.h "runtime")
 #include "xrs_common.h"
+#include "dtype_dispatch.h"
 #include "build_id.h"                // generated into the build directory of the flavour being built (Makefile: -I$(BUILD))
 
 using namespace xrs;
@@ -89,18 +90,10 @@ int xrs_cast_f32(const void *src_dev, int src_dtype, float *dst_dev, int64_t n, 
     if (!src_dev || !dst_dev) return fail("xrs_cast_f32: null pointer");
     if (!aligned16(dst_dev)) return fail("xrs_cast_f32: destination must be 16-byte aligned");
     hipStream_t s = as_stream(stream);
-    switch (src_dtype) {
-        case XRS_DT_I8: return launch_cast<int8_t>(src_dev, dst_dev, n, s);
-        case XRS_DT_U8: return launch_cast<uint8_t>(src_dev, dst_dev, n, s);
-        case XRS_DT_I16: return launch_cast<int16_t>(src_dev, dst_dev, n, s);
-        case XRS_DT_U16: return launch_cast<uint16_t>(src_dev, dst_dev, n, s);
-        case XRS_DT_I32: return launch_cast<int32_t>(src_dev, dst_dev, n, s);
-        case XRS_DT_U32: return launch_cast<uint32_t>(src_dev, dst_dev, n, s);
-        case XRS_DT_I64: return launch_cast<int64_t>(src_dev, dst_dev, n, s);
-        case XRS_DT_U64: return launch_cast<uint64_t>(src_dev, dst_dev, n, s);
-        case XRS_DT_F64: return launch_cast<double>(src_dev, dst_dev, n, s);
-        default: return fail("xrs_cast_f32: unknown source dtype code %d", src_dtype);
-    }
+    int rc = 0;
+    if (!with_dtype<DT_NO_F32>(src_dtype, [&](auto t) { rc = launch_cast<dtype_of<decltype(t)>>(src_dev, dst_dev, n, s); }))
+        return fail("xrs_cast_f32: unknown source dtype code %d", src_dtype);
+    return rc;
 }
 
 int xrs_copy_f32(const float *src_dev, float *dst_dev, int64_t n, void *stream) {
