@@ -25,6 +25,7 @@
 #pragma clang fp contract(off)
 
 #include "xrs_common.h"
+#include "workspace.h"
 
 #include <chrono>
 #include <hipcub/hipcub.hpp>
@@ -32,6 +33,7 @@
 namespace {
 
 using xrs::as_stream;
+using xrs::Carver;
 using xrs::fail;
 using u32 = uint32_t;
 using u64 = unsigned long long;
@@ -54,8 +56,6 @@ struct Geom {
     int jbits;                                  // bits of a key below the cell number
     int spread_on;                              // spread >= 1: centres publish and add v * 0.0
 };
-
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 __host__ __device__ inline long isqrt_floor(long r) {
     long m = (long)sqrt((double)r);
@@ -196,15 +196,20 @@ __global__ __launch_bounds__(BLOCK) void bump_fold_kernel(const u64 *__restrict_
     if (threadIdx.x == 0 && block_retired) atomicAdd(&ctrl->retired, (u64)block_retired);
 }
 
-struct Plan {
+struct Work {
     long cap;               // events a chunk may hold
     long chunk;             // bumps of a chunk
     long footprint;
-    size_t keys_off[2], seg_off, offs_off, v_off, flag_off, ctrl_off, cub_off, cub_bytes, bytes;
+    u64 *keys[2];
+    u32 *seg_cur, *offs, *flag;
+    double *v;
+    Ctrl *ctrl;
+    void *cub;
+    size_t cub_bytes, bytes;
 };
 
 // nullptr, or why the arguments are refused
-const char *make_plan(long count, long width, long height, long spread, long max_events, Plan &p) {
+const char *carve(void *base, long count, long width, long height, long spread, long max_events, Work &p) {
     if (count < 0 || count > (1L << 32) - 2) return "a count of 0 .. 2^32 - 2 bumps is needed";
     if (width < 1 || height < 1) return "width and height of at least 1 are needed";
     if (width >= MAX_CELLS || height >= MAX_CELLS || width * height > MAX_CELLS) return "at most 2^31 cells";
@@ -219,22 +224,21 @@ const char *make_plan(long count, long width, long height, long spread, long max
     p.chunk = cap / p.footprint;
     if (p.chunk > n) p.chunk = n;
     const long segs = cap < width * height ? cap : width * height;
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at += align256(bytes); return o; };
-    p.keys_off[0] = take((size_t)cap * sizeof(u64));
-    p.keys_off[1] = take((size_t)cap * sizeof(u64));
-    p.seg_off = take((size_t)segs * sizeof(u32));
-    p.offs_off = take((size_t)(p.chunk + 1) * sizeof(u32));
-    p.v_off = take((size_t)p.chunk * sizeof(double));
-    p.flag_off = take((size_t)p.chunk * sizeof(u32));
-    p.ctrl_off = take(sizeof(Ctrl));
+    Carver c(base);
+    p.keys[0] = c.take<u64>(cap);
+    p.keys[1] = c.take<u64>(cap);
+    p.seg_cur = c.take<u32>(segs);
+    p.offs = c.take<u32>(p.chunk + 1);
+    p.v = c.take<double>(p.chunk);
+    p.flag = c.take<u32>(p.chunk);
+    p.ctrl = c.take<Ctrl>(1);
     size_t a = 0, b = 0;
     hipcub::DoubleBuffer<u64> dk(nullptr, nullptr);
     (void)hipcub::DeviceRadixSort::SortKeys(nullptr, a, dk, (int)cap);
     (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, (u32 *)nullptr, (u32 *)nullptr, (int)(p.chunk + 1));
     p.cub_bytes = a > b ? a : b;
-    p.cub_off = take(p.cub_bytes);
-    p.bytes = at;
+    p.cub = c.take<char>(p.cub_bytes);
+    p.bytes = c.at();
     return nullptr;
 }
 
@@ -247,14 +251,14 @@ double seconds_since(std::chrono::steady_clock::time_point t0) {
 extern "C" {
 
 size_t xrs_bump_workspace_bytes(int64_t count, int64_t width, int64_t height, int64_t spread, int64_t max_events) {
-    Plan p = {};
-    return make_plan(count, width, height, spread, max_events, p) ? 0 : p.bytes;
+    Work p = {};
+    return carve(nullptr, count, width, height, spread, max_events, p) ? 0 : p.bytes;
 }
 
 int xrs_bump_f64(const uint16_t *locs_dev, const double *heights_dev, int64_t count, int64_t width, int64_t height, int64_t spread,
                  double *out_dev, void *work_dev, size_t work_bytes, int64_t max_events, int64_t *status, void *stream) {
-    Plan p = {};
-    if (const char *why = make_plan(count, width, height, spread, max_events, p)) {
+    Work p = {};
+    if (const char *why = carve(work_dev, count, width, height, spread, max_events, p)) {
         if (p.footprint > max_events && max_events >= 1 && width >= 1 && height >= 1)
             return fail("xrs_bump_f64: %s (%ld events, capacity %ld)", why, p.footprint, (long)max_events);
         return fail("xrs_bump_f64: %s (count %ld, %ld x %ld, spread %ld, capacity %ld)", why, (long)count, (long)width, (long)height,
@@ -263,14 +267,6 @@ int xrs_bump_f64(const uint16_t *locs_dev, const double *heights_dev, int64_t co
     if (!out_dev || !work_dev || (count > 0 && (!locs_dev || !heights_dev))) return fail("xrs_bump_f64: null pointer");
     if (work_bytes < p.bytes) return fail("xrs_bump_f64: workspace of %zu bytes, %zu needed", work_bytes, p.bytes);
     hipStream_t s = as_stream(stream);
-    char *base = static_cast<char *>(work_dev);
-    u64 *keys[2] = {reinterpret_cast<u64 *>(base + p.keys_off[0]), reinterpret_cast<u64 *>(base + p.keys_off[1])};
-    u32 *seg_cur = reinterpret_cast<u32 *>(base + p.seg_off);
-    u32 *offs = reinterpret_cast<u32 *>(base + p.offs_off);
-    double *v = reinterpret_cast<double *>(base + p.v_off);
-    u32 *flag = reinterpret_cast<u32 *>(base + p.flag_off);
-    Ctrl *ctrl = reinterpret_cast<Ctrl *>(base + p.ctrl_off);
-    void *cub = base + p.cub_off;
 
     Geom g;
     g.width = width;
@@ -290,35 +286,35 @@ int xrs_bump_f64(const uint16_t *locs_dev, const double *heights_dev, int64_t co
         const double *z = heights_dev + b0;
         const unsigned bump_blocks = (nb + 1 + BLOCK - 1) / BLOCK;
         auto t0 = std::chrono::steady_clock::now();
-        XRS_HIP(hipMemsetAsync(ctrl, 0, sizeof(Ctrl), s));
-        XRS_HIP(hipMemsetAsync(flag, 0, (size_t)nb * sizeof(u32), s));
-        hipLaunchKernelGGL(bump_count_kernel, dim3(bump_blocks), dim3(BLOCK), 0, s, locs, nb, g, offs, ctrl);
+        XRS_HIP(hipMemsetAsync(p.ctrl, 0, sizeof(Ctrl), s));
+        XRS_HIP(hipMemsetAsync(p.flag, 0, (size_t)nb * sizeof(u32), s));
+        hipLaunchKernelGGL(bump_count_kernel, dim3(bump_blocks), dim3(BLOCK), 0, s, locs, nb, g, p.offs, p.ctrl);
         XRS_LAUNCH_CHECK();
         size_t cub_bytes = p.cub_bytes;
-        XRS_HIP(hipcub::DeviceScan::ExclusiveSum(cub, cub_bytes, offs, offs, (int)(nb + 1), s));
+        XRS_HIP(hipcub::DeviceScan::ExclusiveSum(p.cub, cub_bytes, p.offs, p.offs, (int)(nb + 1), s));
         u32 total = 0;
         Ctrl seen;
-        XRS_HIP(hipMemcpyAsync(&total, offs + nb, sizeof(u32), hipMemcpyDeviceToHost, s));
-        XRS_HIP(hipMemcpyAsync(&seen, ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, s));
+        XRS_HIP(hipMemcpyAsync(&total, p.offs + nb, sizeof(u32), hipMemcpyDeviceToHost, s));
+        XRS_HIP(hipMemcpyAsync(&seen, p.ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, s));
         XRS_HIP(hipStreamSynchronize(s));
         if (seen.bad_loc)
             return fail("xrs_bump_f64: a location lies outside the %ld x %ld raster (bumps %ld .. %ld)", (long)width, (long)height, b0,
                         b0 + nb - 1);
         if ((long)total > p.cap) return fail("xrs_bump_f64: %u events in a chunk planned for %ld", total, p.cap);
         if (total == 0) continue;                   // (cannot happen: every bump inside the raster has its centre's event)
-        hipLaunchKernelGGL(bump_emit_kernel, dim3(bump_blocks), dim3(BLOCK), 0, s, locs, nb, g, offs, keys[0]);
+        hipLaunchKernelGGL(bump_emit_kernel, dim3(bump_blocks), dim3(BLOCK), 0, s, locs, nb, g, p.offs, p.keys[0]);
         XRS_LAUNCH_CHECK();
         XRS_HIP(hipStreamSynchronize(s));
         t_expand += seconds_since(t0);
 
         t0 = std::chrono::steady_clock::now();
-        hipcub::DoubleBuffer<u64> dk(keys[0], keys[1]);
+        hipcub::DoubleBuffer<u64> dk(p.keys[0], p.keys[1]);
         cub_bytes = p.cub_bytes;
-        XRS_HIP(hipcub::DeviceRadixSort::SortKeys(cub, cub_bytes, dk, (int)total, 0, g.jbits + cbits, s));
+        XRS_HIP(hipcub::DeviceRadixSort::SortKeys(p.cub, cub_bytes, dk, (int)total, 0, g.jbits + cbits, s));
         const u64 *sorted = dk.Current();
-        hipLaunchKernelGGL(bump_heads_kernel, dim3((total + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, sorted, total, g.jbits, seg_cur, ctrl);
+        hipLaunchKernelGGL(bump_heads_kernel, dim3((total + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, sorted, total, g.jbits, p.seg_cur, p.ctrl);
         XRS_LAUNCH_CHECK();
-        XRS_HIP(hipMemcpyAsync(&seen, ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, s));
+        XRS_HIP(hipMemcpyAsync(&seen, p.ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, s));
         XRS_HIP(hipStreamSynchronize(s));
         t_sort += seconds_since(t0);
         const u32 nseg = seen.nseg;
@@ -328,10 +324,10 @@ int xrs_bump_f64(const uint16_t *locs_dev, const double *heights_dev, int64_t co
         t0 = std::chrono::steady_clock::now();
         u64 retired = 0;
         for (u32 pass = 1; retired < total; ++pass) {
-            hipLaunchKernelGGL(bump_fold_kernel, dim3((nseg + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, sorted, total, seg_cur, nseg, locs,
-                               z, v, flag, out_dev, g, pass, ctrl);
+            hipLaunchKernelGGL(bump_fold_kernel, dim3((nseg + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, sorted, total, p.seg_cur, nseg, locs,
+                               z, p.v, p.flag, out_dev, g, pass, p.ctrl);
             XRS_LAUNCH_CHECK();
-            XRS_HIP(hipMemcpyAsync(&seen, ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, s));
+            XRS_HIP(hipMemcpyAsync(&seen, p.ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, s));
             XRS_HIP(hipStreamSynchronize(s));
             if (seen.retired <= retired || seen.retired > total)
                 return fail("xrs_bump_f64: pass %u retired no event (%llu of %u done)", pass, seen.retired, total);

@@ -13,6 +13,7 @@
 // Every comparison is in float64, as Numba compares a float32 / integer cell with float64 bins.
 #include "xrs_common.h"
 #include "dtype_dispatch.h"
+#include "workspace.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -319,7 +320,20 @@ __global__ void sel_decode_kernel(const SelState *st, int nr, double *out) {
     if (r < nr) out[r] = (double)Key<T>::dec((typename Key<T>::K)st->prefix[r]);
 }
 
-inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
+struct SelWork {
+    SelState *st;
+    unsigned *hist;
+    size_t hist_bytes, total;
+};
+inline SelWork carve_select(void *base) {
+    Carver c(base);
+    SelWork w = {};
+    w.st = c.take<SelState>(1);
+    w.hist_bytes = (size_t)MAX_RANKS * NBUCKET * 4;
+    w.hist = c.take_bytes<unsigned>(w.hist_bytes);
+    w.total = c.at();
+    return w;
+}
 inline unsigned sel_blocks(long n) {
     const long b = (n + SEL_THREADS * 16L - 1) / (SEL_THREADS * 16L);
     return (unsigned)(b < 1 ? 1 : (b > SEL_MAX_BLOCKS ? SEL_MAX_BLOCKS : b));
@@ -334,23 +348,20 @@ int select_impl(const T *in, long n, const long long *ranks, int nr, void *work,
     if (nr > MAX_RANKS) return fail("xrs_classify_select: at most %d ranks per call (%d)", MAX_RANKS, nr);
     if (n >= (1L << 32)) return fail("xrs_classify_select: at most 2^32-1 cells per call");
     if (!in || !ranks || !work || !out) return fail("xrs_classify_select: null pointer");
-    const size_t hist_bytes = (size_t)MAX_RANKS * NBUCKET * 4;
-    if (work_bytes < up256(sizeof(SelState)) + hist_bytes)
-        return fail("xrs_classify_select: workspace too small (%zu)", work_bytes);
-    SelState *st = static_cast<SelState *>(work);
-    unsigned *hist = reinterpret_cast<unsigned *>(static_cast<char *>(work) + up256(sizeof(SelState)));
-    hipLaunchKernelGGL(sel_init_kernel, dim3(1), dim3(MAX_RANKS), 0, s, st, ranks, nr);
+    const SelWork w = carve_select(work);
+    if (work_bytes < w.total) return fail("xrs_classify_select: workspace too small (%zu)", work_bytes);
+    hipLaunchKernelGGL(sel_init_kernel, dim3(1), dim3(MAX_RANKS), 0, s, w.st, ranks, nr);
     XRS_LAUNCH_CHECK();
     for (int d = 0; d < n_digits<KB>(); ++d) {
-        XRS_HIP(hipMemsetAsync(hist, 0, hist_bytes, s));
-        hipLaunchKernelGGL((sel_hist_kernel<T>), dim3(sel_blocks(n)), dim3(SEL_THREADS), 0, s, in, n, st, d, hist);
+        XRS_HIP(hipMemsetAsync(w.hist, 0, w.hist_bytes, s));
+        hipLaunchKernelGGL((sel_hist_kernel<T>), dim3(sel_blocks(n)), dim3(SEL_THREADS), 0, s, in, n, w.st, d, w.hist);
         XRS_LAUNCH_CHECK();
-        hipLaunchKernelGGL((sel_scan_kernel<KB>), dim3(nr), dim3(256), 0, s, st, d, hist);
+        hipLaunchKernelGGL((sel_scan_kernel<KB>), dim3(nr), dim3(256), 0, s, w.st, d, w.hist);
         XRS_LAUNCH_CHECK();
-        hipLaunchKernelGGL(sel_dedupe_kernel, dim3(1), dim3(64), 0, s, st, nr);
+        hipLaunchKernelGGL(sel_dedupe_kernel, dim3(1), dim3(64), 0, s, w.st, nr);
         XRS_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL((sel_decode_kernel<T>), dim3(1), dim3(MAX_RANKS), 0, s, st, nr, out);
+    hipLaunchKernelGGL((sel_decode_kernel<T>), dim3(1), dim3(MAX_RANKS), 0, s, w.st, nr, out);
     XRS_LAUNCH_CHECK();
     return 0;
 }
@@ -459,28 +470,38 @@ __global__ void mb_gather_kernel(const typename Key<T>::K *uk, const unsigned *m
 }
 
 template <typename T>
-struct MbPlan {
+struct MbWork {
     using K = typename Key<T>::K;
-    size_t off_k[2], off_u, off_flags, off_m, off_parts, off_bound, off_picked, off_cub, cub_bytes, total;
-    MbPlan(long n, int n_top) {
-        size_t o = 0;
-        for (int i = 0; i < 2; ++i) { off_k[i] = o; o += up256((size_t)n * sizeof(K)); }
-        off_u = o; o += up256((size_t)n * sizeof(K));
-        off_flags = o; o += up256((size_t)n);
-        off_m = o; o += 256;
-        off_parts = o; o += up256(MB_BLOCKS * sizeof(Arg));
-        off_bound = o; o += 256;
-        off_picked = o; o += up256((size_t)(n_top > 0 ? n_top : 1) * 8);
-        size_t t1 = 0, t2 = 0;
-        hipcub::DoubleBuffer<K> dk(nullptr, nullptr);
-        (void)hipcub::DeviceRadixSort::SortKeys(nullptr, t1, dk, (int)n);
-        (void)hipcub::DeviceSelect::Flagged(nullptr, t2, (const K *)nullptr, (const unsigned char *)nullptr, (K *)nullptr,
-                                            (unsigned *)nullptr, (int)n);
-        cub_bytes = up256(t1 > t2 ? t1 : t2) + 256;
-        off_cub = o; o += cub_bytes;
-        total = o;
-    }
+    K *k[2], *uk;
+    unsigned char *flags;
+    unsigned *m;
+    Arg *parts, *bound;
+    long long *picked;
+    void *cub;
+    size_t cub_bytes, total;
 };
+template <typename T>
+MbWork<T> carve_max_breaks(void *base, long n, int n_top) {
+    using K = typename Key<T>::K;
+    Carver c(base);
+    MbWork<T> w = {};
+    for (int i = 0; i < 2; ++i) w.k[i] = c.take<K>(n);
+    w.uk = c.take<K>(n);
+    w.flags = c.take<unsigned char>(n);
+    w.m = c.take_bytes<unsigned>(256);
+    w.parts = c.take<Arg>(MB_BLOCKS);
+    w.bound = c.take_bytes<Arg>(256);
+    w.picked = c.take<long long>(n_top > 0 ? n_top : 1);
+    size_t t1 = 0, t2 = 0;
+    hipcub::DoubleBuffer<K> dk(nullptr, nullptr);
+    (void)hipcub::DeviceRadixSort::SortKeys(nullptr, t1, dk, (int)n);
+    (void)hipcub::DeviceSelect::Flagged(nullptr, t2, (const K *)nullptr, (const unsigned char *)nullptr, (K *)nullptr,
+                                        (unsigned *)nullptr, (int)n);
+    w.cub_bytes = up256(t1 > t2 ? t1 : t2) + 256;
+    w.cub = c.take_bytes(w.cub_bytes);
+    w.total = c.at();
+    return w;
+}
 
 template <typename T>
 int max_breaks_impl(const T *in, long n, int n_top, void *work, size_t work_bytes, double *out, hipStream_t s) {
@@ -488,42 +509,33 @@ int max_breaks_impl(const T *in, long n, int n_top, void *work, size_t work_byte
     if (n <= 0) return fail("xrs_classify_max_breaks: no cells");
     if (n >= (1L << 31)) return fail("xrs_classify_max_breaks: at most 2^31-1 cells per call");
     if (!in || !work || !out) return fail("xrs_classify_max_breaks: null pointer");
-    MbPlan<T> pl(n, n_top);
-    if (work_bytes < pl.total) return fail("xrs_classify_max_breaks: workspace too small (%zu < %zu)", work_bytes, pl.total);
-    char *w = static_cast<char *>(work);
-    K *k0 = reinterpret_cast<K *>(w + pl.off_k[0]), *k1 = reinterpret_cast<K *>(w + pl.off_k[1]);
-    K *uk = reinterpret_cast<K *>(w + pl.off_u);
-    unsigned char *flags = reinterpret_cast<unsigned char *>(w + pl.off_flags);
-    unsigned *m = reinterpret_cast<unsigned *>(w + pl.off_m);
-    Arg *parts = reinterpret_cast<Arg *>(w + pl.off_parts);
-    Arg *bound = reinterpret_cast<Arg *>(w + pl.off_bound);
-    long long *picked = reinterpret_cast<long long *>(w + pl.off_picked);
-    void *cub = w + pl.off_cub;
+    const MbWork<T> w = carve_max_breaks<T>(work, n, n_top);
+    if (work_bytes < w.total) return fail("xrs_classify_max_breaks: workspace too small (%zu < %zu)", work_bytes, w.total);
     const unsigned grid = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL((mb_keys_kernel<T>), dim3(grid), dim3(256), 0, s, in, n, k0);
+    hipLaunchKernelGGL((mb_keys_kernel<T>), dim3(grid), dim3(256), 0, s, in, n, w.k[0]);
     XRS_LAUNCH_CHECK();
-    hipcub::DoubleBuffer<K> dk(k0, k1);
-    size_t cb = pl.cub_bytes;
-    XRS_HIP(hipcub::DeviceRadixSort::SortKeys(cub, cb, dk, (int)n, 0, (int)sizeof(K) * 8, s));
-    hipLaunchKernelGGL((mb_heads_kernel<K>), dim3(grid), dim3(256), 0, s, dk.Current(), n, flags);
+    hipcub::DoubleBuffer<K> dk(w.k[0], w.k[1]);
+    size_t cb = w.cub_bytes;
+    XRS_HIP(hipcub::DeviceRadixSort::SortKeys(w.cub, cb, dk, (int)n, 0, (int)sizeof(K) * 8, s));
+    hipLaunchKernelGGL((mb_heads_kernel<K>), dim3(grid), dim3(256), 0, s, dk.Current(), n, w.flags);
     XRS_LAUNCH_CHECK();
-    cb = pl.cub_bytes;
-    XRS_HIP(hipcub::DeviceSelect::Flagged(cub, cb, dk.Current(), flags, uk, m, (int)n, s));
+    cb = w.cub_bytes;
+    XRS_HIP(hipcub::DeviceSelect::Flagged(w.cub, cb, dk.Current(), w.flags, w.uk, w.m, (int)n, s));
     if (n_top < 0) {
-        hipLaunchKernelGGL((mb_gather_kernel<T>), dim3(grid), dim3(256), 0, s, uk, m, picked, n_top, out);
+        hipLaunchKernelGGL((mb_gather_kernel<T>), dim3(grid), dim3(256), 0, s, w.uk, w.m, w.picked, n_top, out);
         XRS_LAUNCH_CHECK();
         return 0;
     }
     const Arg none{0.0, -1};
-    XRS_HIP(hipMemcpyAsync(bound, &none, sizeof(Arg), hipMemcpyHostToDevice, s));
+    XRS_HIP(hipMemcpyAsync(w.bound, &none, sizeof(Arg), hipMemcpyHostToDevice, s));
     const unsigned mb = grid < (unsigned)MB_BLOCKS ? grid : (unsigned)MB_BLOCKS;
     for (int j = 0; j < n_top; ++j) {
-        hipLaunchKernelGGL((mb_argmax_kernel<T>), dim3(mb), dim3(256), 0, s, uk, m, bound, parts);
+        hipLaunchKernelGGL((mb_argmax_kernel<T>), dim3(mb), dim3(256), 0, s, w.uk, w.m, w.bound, w.parts);
         XRS_LAUNCH_CHECK();
-        hipLaunchKernelGGL(mb_pick_kernel, dim3(1), dim3(256), 0, s, parts, (int)mb, bound, picked + j);
+        hipLaunchKernelGGL(mb_pick_kernel, dim3(1), dim3(256), 0, s, w.parts, (int)mb, w.bound, w.picked + j);
         XRS_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL((mb_gather_kernel<T>), dim3(1), dim3(256), 0, s, uk, m, picked, n_top, out);
+    hipLaunchKernelGGL((mb_gather_kernel<T>), dim3(1), dim3(256), 0, s, w.uk, w.m, w.picked, n_top, out);
     XRS_LAUNCH_CHECK();
     return 0;
 }
@@ -580,9 +592,10 @@ extern "C" {
 
 size_t xrs_classify_workspace_bytes(int64_t n, int values_f64) {
     const long m = n > 0 ? n : 1;
-    size_t a = up256(sizeof(SelState)) + (size_t)MAX_RANKS * NBUCKET * 4;
+    size_t a = carve_select(nullptr).total;
     const size_t r = up256(RED_BLOCKS * sizeof(Part));
-    const size_t mb = values_f64 ? MbPlan<double>(m, MAX_RANKS).total : MbPlan<float>(m, MAX_RANKS).total;
+    const size_t mb = values_f64 ? carve_max_breaks<double>(nullptr, m, MAX_RANKS).total
+                                 : carve_max_breaks<float>(nullptr, m, MAX_RANKS).total;
     a = a > r ? a : r;
     return a > mb ? a : mb;
 }

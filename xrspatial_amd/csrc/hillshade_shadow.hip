@@ -103,7 +103,7 @@ int shadow_impl(const T *z, long rows, long cols, double scale, double zmin, dou
     if (tiles_x * tiles_y >= (1L << 31) || blocks_x * blocks_y >= (1L << 31))
         return fail("xrs_hillshade_shadow: raster too large for one call (%ld x %ld)", rows, cols);
     float *zv = static_cast<float *>(work);
-    float *bmax = reinterpret_cast<float *>(static_cast<char *>(work) + align256((size_t)rows * (size_t)cols * sizeof(float)));
+    float *bmax = reinterpret_cast<float *>(static_cast<char *>(work) + up256((size_t)rows * (size_t)cols * sizeof(float)));
     // the vertex heights as the kernels see them: float32 of the scaled bounds (the rounding is monotonic)
     const double vmin = (double)(float)(zmin * scale), vmax = (double)(float)(zmax * scale);
     if (rows >= 3 && cols >= 3) {                                  // (else every cell is a border cell and no height is read)

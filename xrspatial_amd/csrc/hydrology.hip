@@ -19,6 +19,7 @@
 //   finish      uint32 -> float64, NaN at NaN cells.
 #include "xrs_common.h"
 #include "dtype_dispatch.h"
+#include "workspace.h"
 
 #include <chrono>
 #include <cmath>
@@ -44,30 +45,6 @@ constexpr int ROW_WORDS = SLOTS * SLOT_STRIDE;                           // live
 constexpr int BAD_WORD = (MAX_ROUNDS + 1) * ROW_WORDS;                   // then the invalid-code word
 constexpr int HEAD_WORDS = BAD_WORD + 64;
 static_assert(HEAD_WORDS % 64 == 0 && 40 + MAX_ROUNDS <= XRS_FLOW_STATUS_WORDS, "head / status layout");
-
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-struct Plan {
-    size_t anc_off[2], s_off, d_off[2], root_off[2], total;
-};
-Plan plan(size_t cells, int want) {
-    const size_t plane = up256(cells * 4);
-    Plan p = {};
-    size_t at = HEAD_WORDS * 4;
-    p.anc_off[0] = at; at += plane;
-    p.anc_off[1] = at; at += plane;
-    if (want & XRS_FLOW_ACCUMULATION) {
-        p.s_off = at; at += plane;
-        p.d_off[0] = at; at += plane;
-        p.d_off[1] = at; at += plane;
-    }
-    if (want & XRS_FLOW_BASINS) {
-        p.root_off[0] = at; at += plane;
-        p.root_off[1] = at; at += plane;
-    }
-    p.total = at;
-    return p;
-}
 
 // ------------------------------------------------------------------ direction
 // One cell, one load and one store per thread left the kernel waiting on its own loads (0.43 ms for 8192^2 float32 cells
@@ -256,7 +233,22 @@ __global__ void __launch_bounds__(SPAN) flow_finish_kernel(const float *__restri
 
 struct Buffers {
     unsigned *head, *anc[2], *S, *D[2], *root[2];
+    size_t total;
 };
+Buffers carve(void *base, size_t cells, int want) {
+    Carver c(base);
+    Buffers b = {};
+    b.head = c.take<unsigned>(HEAD_WORDS);
+    for (int i = 0; i < 2; ++i) b.anc[i] = c.take<unsigned>(cells);
+    if (want & XRS_FLOW_ACCUMULATION) {
+        b.S = c.take<unsigned>(cells);
+        for (int i = 0; i < 2; ++i) b.D[i] = c.take<unsigned>(cells);
+    }
+    if (want & XRS_FLOW_BASINS)
+        for (int i = 0; i < 2; ++i) b.root[i] = c.take<unsigned>(cells);
+    b.total = c.at();
+    return b;
+}
 
 template <bool ACC, bool BASIN>
 void launch_decode(const float *dir, long rows, long cols, const Buffers &b, unsigned grid, hipStream_t s) {
@@ -324,7 +316,7 @@ int xrs_flow_direction(const void *data_dev, int dtype, int64_t rows, int64_t co
 size_t xrs_flow_workspace_bytes(int64_t rows, int64_t cols, int want) {
     if (rows <= 0 || cols <= 0 || !(want & (XRS_FLOW_ACCUMULATION | XRS_FLOW_BASINS))) return 0;
     if ((uint64_t)rows > XRS_FLOW_MAX_CELLS / (uint64_t)cols) return 0;
-    return plan((size_t)rows * (size_t)cols, want).total;
+    return carve(nullptr, (size_t)rows * (size_t)cols, want).total;
 }
 
 int xrs_flow_accumulate(const float *dir_dev, int64_t rows, int64_t cols, void *work_dev, double *acc_out_dev, double *basin_out_dev,
@@ -342,16 +334,7 @@ int xrs_flow_accumulate(const float *dir_dev, int64_t rows, int64_t cols, void *
     hipStream_t s = as_stream(stream);
     const bool acc = acc_out_dev != nullptr, basin = basin_out_dev != nullptr, timed = flags & XRS_FLOW_TIMED;
     const long cells = (long)rows * (long)cols;
-    const Plan pl = plan((size_t)cells, (acc ? XRS_FLOW_ACCUMULATION : 0) | (basin ? XRS_FLOW_BASINS : 0));
-    char *base = static_cast<char *>(work_dev);
-    Buffers b = {};
-    b.head = (unsigned *)base;
-    for (int i = 0; i < 2; ++i) {
-        b.anc[i] = (unsigned *)(base + pl.anc_off[i]);
-        if (acc) b.D[i] = (unsigned *)(base + pl.d_off[i]);
-        if (basin) b.root[i] = (unsigned *)(base + pl.root_off[i]);
-    }
-    if (acc) b.S = (unsigned *)(base + pl.s_off);
+    const Buffers b = carve(work_dev, (size_t)cells, (acc ? XRS_FLOW_ACCUMULATION : 0) | (basin ? XRS_FLOW_BASINS : 0));
     const unsigned grid = (unsigned)((cells + SPAN * ITEMS - 1) / (SPAN * ITEMS));      // < 2^21 blocks
     const int bound = bit_length((uint64_t)cells);                       // a path has at most cells - 1 < 2^bound steps
     std::vector<unsigned> slots((size_t)(GROUP + 1) * ROW_WORDS);

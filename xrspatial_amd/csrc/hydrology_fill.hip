@@ -25,6 +25,7 @@
 //            No loop depends on the data without a bound, nothing waits on another block.
 #include "xrs_common.h"
 #include "dtype_dispatch.h"
+#include "workspace.h"
 
 #include <chrono>
 #include <cmath>
@@ -49,8 +50,6 @@ constexpr int HEAD_WORDS = TOTAL_WORD + 64;
 constexpr int ROUNDS_KEPT = XRS_FILL_STATUS_ROUNDS;
 static_assert(TILE == 64 && STRIP == 16, "a wave's lanes are a tile's columns");
 static_assert(8 + 3 * ROUNDS_KEPT <= XRS_FILL_STATUS_WORDS, "status layout");
-
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 template <typename T>
 __device__ __forceinline__ T nan_of() { return (T)nan_f32(); }
@@ -297,14 +296,13 @@ struct Work {
 };
 Work carve(void *base, size_t rows, size_t cols, bool with_d) {
     const size_t tiles = ((rows + TILE - 1) / TILE) * ((cols + TILE - 1) / TILE);
-    char *p = static_cast<char *>(base);
+    Carver c(base);
     Work w = {};
-    size_t at = 0;
-    w.head = (unsigned *)(p + at); at += up256((size_t)HEAD_WORDS * 4);
-    w.flags = (unsigned *)(p + at); at += up256(tiles * 4);
-    w.list = (unsigned *)(p + at); at += up256(tiles * 4);
-    if (with_d) { w.d = (unsigned *)(p + at); at += up256(rows * cols * 4); }
-    w.total = at;
+    w.head = c.take<unsigned>(HEAD_WORDS);
+    w.flags = c.take<unsigned>(tiles);
+    w.list = c.take<unsigned>(tiles);
+    if (with_d) w.d = c.take<unsigned>(rows * cols);
+    w.total = c.at();
     return w;
 }
 

@@ -12,6 +12,7 @@
 #pragma clang fp contract(off)
 
 #include "xrs_common.h"
+#include "workspace.h"
 
 #include <cmath>
 
@@ -19,11 +20,10 @@ namespace {
 
 using xrs::as_stream;
 using xrs::fail;
+using xrs::up256;
 
 constexpr int BLOCK = 64;               // one wave per workgroup: the ~n / 64 waves of a column spread over all CUs
 constexpr long N_MAX = 1L << 24;        // the lower class limits are float32 row numbers: exact below 2^24
-
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // the reference's initial tables, and rows 0 and 1 of both working columns (V[0][j] is never read, V[1][j] = 0)
 __global__ __launch_bounds__(256) void jenks_init_kernel(float *__restrict__ limits, float *__restrict__ var, float *__restrict__ col_a,
@@ -106,7 +106,7 @@ extern "C" {
 
 size_t xrs_jenks_workspace_bytes(int64_t n, int k) {
     if (n < 1 || n >= N_MAX || k < 1) return 0;
-    return 2 * align256((size_t)(n + 1) * sizeof(float));
+    return 2 * up256((size_t)(n + 1) * sizeof(float));
 }
 
 int xrs_jenks_matrices_f32(const float *sorted_dev, int64_t n, int k, float *lower_class_limits_dev, float *var_combinations_dev,
@@ -121,7 +121,7 @@ int xrs_jenks_matrices_f32(const float *sorted_dev, int64_t n, int k, float *low
         return fail("xrs_jenks_matrices_f32: workspace of %zu bytes, %zu needed", work_bytes, xrs_jenks_workspace_bytes(n, k));
     hipStream_t s = as_stream(stream);
     float *col[2] = {static_cast<float *>(work_dev),
-                     reinterpret_cast<float *>(static_cast<char *>(work_dev) + align256((size_t)(n + 1) * sizeof(float)))};
+                     reinterpret_cast<float *>(static_cast<char *>(work_dev) + up256((size_t)(n + 1) * sizeof(float)))};
     const long cells = (n + 1) * ((long)k + 1);
     hipLaunchKernelGGL(jenks_init_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, lower_class_limits_dev,
                        var_combinations_dev, col[0], col[1], (long)n, k);

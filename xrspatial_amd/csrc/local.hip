@@ -17,6 +17,7 @@
 //              first occurrence in row-major order; sorting the classes by that cell gives the reference's ids.
 #include "xrs_common.h"
 #include "dtype_dispatch.h"
+#include "workspace.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -482,35 +483,43 @@ __global__ void __launch_bounds__(256) local_gather_kernel(const LocalArgs args,
     }
 }
 
-inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-struct CombinePlan {
-    size_t off_idx[2], off_key[2], off_cls, off_scan, off_bad, off_small, off_cub, cub_bytes, total;
-    explicit CombinePlan(long n) {
-        size_t o = 0;
-        for (int i = 0; i < 2; ++i) { off_idx[i] = o; o += up256((size_t)n * 4); }
-        for (int i = 0; i < 2; ++i) { off_key[i] = o; o += up256((size_t)n * 8) + 256; }     // later: two arrays of n words each, the second 256-aligned
-        off_cls = o; o += up256((size_t)n * 4);
-        off_scan = o; o += up256((size_t)n * 4);                                       // later: the classes' ranks
-        off_bad = o; o += up256((size_t)n);
-        off_small = o; o += 256;                                                       // { class count, any NaN cell }
-        size_t t1 = 0, t2 = 0, t3 = 0, t4 = 0;
-        hipcub::DoubleBuffer<u64> dk(nullptr, nullptr);
-        hipcub::DoubleBuffer<unsigned> dc(nullptr, nullptr), di(nullptr, nullptr);
-        (void)hipcub::DeviceRadixSort::SortPairs(nullptr, t1, dk, di, (int)n);
-        (void)hipcub::DeviceRadixSort::SortPairs(nullptr, t2, dc, di, (int)n);
-        (void)hipcub::DeviceScan::InclusiveSum(nullptr, t3, (unsigned *)nullptr, (unsigned *)nullptr, (int)n);
-        (void)hipcub::DeviceRadixSort::SortPairs(nullptr, t4, (const unsigned *)nullptr, (unsigned *)nullptr, (const unsigned *)nullptr,
-                                                 (unsigned *)nullptr, (int)n);
-        size_t m = t1 > t2 ? t1 : t2;
-        m = m > t3 ? m : t3;
-        m = m > t4 ? m : t4;
-        cub_bytes = up256(m) + 256;
-        off_cub = o; o += cub_bytes;
-        total = o;
-    }
-    size_t off_first_sorted(long n) const { return off_key[0] + up256((size_t)n * 4); }
+struct CombineWork {
+    unsigned *idx[2], *cls, *scan, *small;
+    u64 *key[2];
+    unsigned *half[2][2];           // key[i] seen again, once the value keys are done with: two arrays of n words each
+    unsigned char *bad;
+    void *cub;
+    size_t cub_bytes, total;
 };
+CombineWork carve_combine(void *base, long n) {
+    Carver c(base);
+    CombineWork w = {};
+    for (int i = 0; i < 2; ++i) w.idx[i] = c.take<unsigned>(n);
+    for (int i = 0; i < 2; ++i) {
+        Carver halves(c.take_bytes(up256((size_t)n * 8) + 256));   // (256 more: the second half is 256-aligned too)
+        w.key[i] = halves.take<u64>(0);
+        for (int h = 0; h < 2; ++h) w.half[i][h] = halves.take<unsigned>(n);
+    }
+    w.cls = c.take<unsigned>(n);
+    w.scan = c.take<unsigned>(n);                                   // later: the classes' ranks
+    w.bad = c.take<unsigned char>(n);
+    w.small = c.take_bytes<unsigned>(256);                          // { class count, any NaN cell }
+    size_t t1 = 0, t2 = 0, t3 = 0, t4 = 0;
+    hipcub::DoubleBuffer<u64> dk(nullptr, nullptr);
+    hipcub::DoubleBuffer<unsigned> dc(nullptr, nullptr), di(nullptr, nullptr);
+    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, t1, dk, di, (int)n);
+    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, t2, dc, di, (int)n);
+    (void)hipcub::DeviceScan::InclusiveSum(nullptr, t3, (unsigned *)nullptr, (unsigned *)nullptr, (int)n);
+    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, t4, (const unsigned *)nullptr, (unsigned *)nullptr, (const unsigned *)nullptr,
+                                             (unsigned *)nullptr, (int)n);
+    size_t m = t1 > t2 ? t1 : t2;
+    m = m > t3 ? m : t3;
+    m = m > t4 ? m : t4;
+    w.cub_bytes = up256(m) + 256;
+    w.cub = c.take_bytes(w.cub_bytes);
+    w.total = c.at();
+    return w;
+}
 
 }  // namespace
 
@@ -576,7 +585,7 @@ int xrs_local_cells(int op, const void *const *planes, const int *dtypes, int n_
 size_t xrs_local_combine_workspace_bytes(int64_t n, int n_planes) {
     (void)n_planes;
     if (n <= 0 || n >= (1LL << 31)) return 256;
-    return CombinePlan(n).total;
+    return carve_combine(nullptr, n).total;
 }
 
 int xrs_local_combine(const void *const *planes, const int *dtypes, int n_planes, int64_t n, void *work_dev, size_t work_bytes,
@@ -590,65 +599,54 @@ int xrs_local_combine(const void *const *planes, const int *dtypes, int n_planes
     if (n >= (1LL << 31)) return fail("%s: at most 2^31-1 cells per call", who);
     if (n == 0) { *n_classes = 0; return 0; }
     if (!work_dev) return fail("%s: null pointer (workspace)", who);
-    const CombinePlan pl(n);
-    if (work_bytes < pl.total) return fail("%s: workspace too small (%zu < %zu)", who, work_bytes, pl.total);
+    const CombineWork w = carve_combine(work_dev, n);
+    if (work_bytes < w.total) return fail("%s: workspace too small (%zu < %zu)", who, work_bytes, w.total);
     hipStream_t s = as_stream(stream);
-    char *w = static_cast<char *>(work_dev);
     if (first_cells_dev) {                                     // second call: the list the first call left in the workspace
         if (*n_classes < 0 || *n_classes > first_capacity || *n_classes > n) return fail("%s: room for %lld first cells, %lld classes", who, (long long)first_capacity, (long long)*n_classes);
-        if (*n_classes) XRS_HIP(hipMemcpyAsync(first_cells_dev, w + pl.off_first_sorted(n), (size_t)*n_classes * 4, hipMemcpyDeviceToDevice, s));
+        if (*n_classes) XRS_HIP(hipMemcpyAsync(first_cells_dev, w.half[0][1], (size_t)*n_classes * 4, hipMemcpyDeviceToDevice, s));
         return 0;
     }
     if (!out_dev) return fail("%s: null pointer (out)", who);
-    unsigned *idx[2] = {reinterpret_cast<unsigned *>(w + pl.off_idx[0]), reinterpret_cast<unsigned *>(w + pl.off_idx[1])};
-    u64 *key[2] = {reinterpret_cast<u64 *>(w + pl.off_key[0]), reinterpret_cast<u64 *>(w + pl.off_key[1])};
-    unsigned *cls = reinterpret_cast<unsigned *>(w + pl.off_cls);
-    unsigned *scan = reinterpret_cast<unsigned *>(w + pl.off_scan);
-    unsigned char *bad = reinterpret_cast<unsigned char *>(w + pl.off_bad);
-    unsigned *small = reinterpret_cast<unsigned *>(w + pl.off_small);
-    void *cub = w + pl.off_cub;
     const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    XRS_HIP(hipMemsetAsync(small, 0, 256, s));
-    hipLaunchKernelGGL(combine_mask_kernel, grid, block, 0, s, args, n_planes, (long)n, bad, idx[0], cls, small + 1);
+    XRS_HIP(hipMemsetAsync(w.small, 0, 256, s));
+    hipLaunchKernelGGL(combine_mask_kernel, grid, block, 0, s, args, n_planes, (long)n, w.bad, w.idx[0], w.cls, w.small + 1);
     XRS_LAUNCH_CHECK();
-    hipcub::DoubleBuffer<unsigned> di(idx[0], idx[1]);
+    hipcub::DoubleBuffer<unsigned> di(w.idx[0], w.idx[1]);
     unsigned host_small[2] = {2u, 0u};                         // classes so far: the valid cells and the NaN cells
     for (int j = 0; j < n_planes; ++j) {
-        hipLaunchKernelGGL(combine_key_kernel, grid, block, 0, s, args.p[j], (int)args.dt[j], di.Current(), bad, (long)n, key[0]);
+        hipLaunchKernelGGL(combine_key_kernel, grid, block, 0, s, args.p[j], (int)args.dt[j], di.Current(), w.bad, (long)n, w.key[0]);
         XRS_LAUNCH_CHECK();
-        hipcub::DoubleBuffer<u64> dk(key[0], key[1]);
-        size_t cb = pl.cub_bytes;
-        XRS_HIP(hipcub::DeviceRadixSort::SortPairs(cub, cb, dk, di, (int)n, 0, 8 * dtype_bytes(args.dt[j]), s));
-        unsigned *ck[2] = {reinterpret_cast<unsigned *>(key[0]), reinterpret_cast<unsigned *>(key[1])};     // (the value keys are done with)
-        hipLaunchKernelGGL(combine_class_key_kernel, grid, block, 0, s, cls, di.Current(), (long)n, ck[0]);
+        hipcub::DoubleBuffer<u64> dk(w.key[0], w.key[1]);
+        size_t cb = w.cub_bytes;
+        XRS_HIP(hipcub::DeviceRadixSort::SortPairs(w.cub, cb, dk, di, (int)n, 0, 8 * dtype_bytes(args.dt[j]), s));
+        unsigned *ck[2] = {w.half[0][0], w.half[1][0]};                                // (the value keys are done with)
+        hipLaunchKernelGGL(combine_class_key_kernel, grid, block, 0, s, w.cls, di.Current(), (long)n, ck[0]);
         XRS_LAUNCH_CHECK();
         int cbits = 1;
         while (cbits < 32 && (1ull << cbits) < (u64)host_small[0]) ++cbits;
         hipcub::DoubleBuffer<unsigned> dc(ck[0], ck[1]);
-        cb = pl.cub_bytes;
-        XRS_HIP(hipcub::DeviceRadixSort::SortPairs(cub, cb, dc, di, (int)n, 0, cbits, s));
-        hipLaunchKernelGGL(combine_flag_kernel, grid, block, 0, s, args.p[j], (int)args.dt[j], di.Current(), bad, dc.Current(), (long)n, scan);
+        cb = w.cub_bytes;
+        XRS_HIP(hipcub::DeviceRadixSort::SortPairs(w.cub, cb, dc, di, (int)n, 0, cbits, s));
+        hipLaunchKernelGGL(combine_flag_kernel, grid, block, 0, s, args.p[j], (int)args.dt[j], di.Current(), w.bad, dc.Current(), (long)n, w.scan);
         XRS_LAUNCH_CHECK();
-        cb = pl.cub_bytes;
-        XRS_HIP(hipcub::DeviceScan::InclusiveSum(cub, cb, scan, scan, (int)n, s));
-        hipLaunchKernelGGL(combine_scatter_kernel, grid, block, 0, s, di.Current(), scan, (long)n, cls, small);
+        cb = w.cub_bytes;
+        XRS_HIP(hipcub::DeviceScan::InclusiveSum(w.cub, cb, w.scan, w.scan, (int)n, s));
+        hipLaunchKernelGGL(combine_scatter_kernel, grid, block, 0, s, di.Current(), w.scan, (long)n, w.cls, w.small);
         XRS_LAUNCH_CHECK();
-        XRS_HIP(hipMemcpyAsync(host_small, small, 8, hipMemcpyDeviceToHost, s));
+        XRS_HIP(hipMemcpyAsync(host_small, w.small, 8, hipMemcpyDeviceToHost, s));
         XRS_HIP(hipStreamSynchronize(s));
         if (host_small[0] < 1 || (int64_t)host_small[0] > n) return fail("%s: internal error: %u classes of %lld cells", who, host_small[0], (long long)n);
     }
     const long total = host_small[0];
-    unsigned *first = reinterpret_cast<unsigned *>(w + pl.off_key[0]);
-    unsigned *first_sorted = reinterpret_cast<unsigned *>(w + pl.off_first_sorted(n));
-    unsigned *cid = reinterpret_cast<unsigned *>(w + pl.off_key[1]);
-    unsigned *cid_sorted = reinterpret_cast<unsigned *>(w + pl.off_key[1] + up256((size_t)n * 4));
-    hipLaunchKernelGGL(combine_first_kernel, grid, block, 0, s, di.Current(), scan, bad, (long)n, first, cid);
+    unsigned *first = w.half[0][0], *first_sorted = w.half[0][1], *cid = w.half[1][0], *cid_sorted = w.half[1][1];
+    hipLaunchKernelGGL(combine_first_kernel, grid, block, 0, s, di.Current(), w.scan, w.bad, (long)n, first, cid);
     XRS_LAUNCH_CHECK();
-    size_t cb = pl.cub_bytes;
-    XRS_HIP(hipcub::DeviceRadixSort::SortPairs(cub, cb, (const unsigned *)first, first_sorted, (const unsigned *)cid, cid_sorted, (int)total, 0, 32, s));
-    hipLaunchKernelGGL(combine_rank_kernel, dim3((unsigned)((total + 255) / 256)), block, 0, s, cid_sorted, total, scan);
+    size_t cb = w.cub_bytes;
+    XRS_HIP(hipcub::DeviceRadixSort::SortPairs(w.cub, cb, (const unsigned *)first, first_sorted, (const unsigned *)cid, cid_sorted, (int)total, 0, 32, s));
+    hipLaunchKernelGGL(combine_rank_kernel, dim3((unsigned)((total + 255) / 256)), block, 0, s, cid_sorted, total, w.scan);
     XRS_LAUNCH_CHECK();
-    hipLaunchKernelGGL(combine_out_kernel, grid, block, 0, s, cls, bad, scan, (long)n, out_dev);
+    hipLaunchKernelGGL(combine_out_kernel, grid, block, 0, s, w.cls, w.bad, w.scan, (long)n, out_dev);
     XRS_LAUNCH_CHECK();
     XRS_HIP(hipStreamSynchronize(s));
     *n_classes = total - (host_small[1] ? 1 : 0);

@@ -33,6 +33,7 @@
 
 #include "xrs_common.h"
 #include "wave_reduce.h"
+#include "workspace.h"
 
 #include <cmath>
 
@@ -214,12 +215,10 @@ size_t table_cells(long rows, long cols, int bshift) {
     return (size_t)(by > 0 ? by : 0) * (size_t)(bx > 0 ? bx : 0);
 }
 
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // the float32 vertex heights, then the largest table of block maxima
 size_t mesh_workspace_bytes(long rows, long cols) {
     if (rows < 1 || cols < 1) return 0;
-    return align256((size_t)rows * (size_t)cols * sizeof(float)) + align256((table_cells(rows, cols, BSHIFT_MIN) + 1) * sizeof(float));
+    return up256((size_t)rows * (size_t)cols * sizeof(float)) + up256((table_cells(rows, cols, BSHIFT_MIN) + 1) * sizeof(float));
 }
 
 }  // namespace

@@ -34,6 +34,7 @@
 #include "dtype_dispatch.h"
 #include "value_match.h"
 #include "wave_reduce.h"
+#include "workspace.h"
 
 #include <cmath>
 #include <type_traits>
@@ -54,25 +55,29 @@ constexpr long long NO_KEY = 0x7fffffffffffffffLL;
 constexpr int ST_START_ROW = 0, ST_START_COL = 1, ST_GOAL_ROW = 2, ST_FLAGS = 4, ST_A = 5, ST_B = 6, ST_ERROR = 8, ST_VISITS = 9;
 constexpr int ST_WORDS = 16;
 
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-struct Plan {
-    size_t field_off, dirty_off[2], changed_off, status_off, partial_off, total;
+struct Work {
+    uint64_t *field;
+    int *dirty[2], *changed;
+    long long *st, *partial;
+    size_t zero_bytes, total;       // zero_bytes from dirty[0]: both dirty arrays, changed, status -- cleared per call
     long tiles_x, tiles_y;
 };
-Plan plan(size_t rows, size_t cols) {
-    Plan p;
-    p.tiles_x = (long)((cols + TW - 1) / TW);
-    p.tiles_y = (long)((rows + TH - 1) / TH);
-    const size_t tiles = (size_t)p.tiles_x * (size_t)p.tiles_y;
-    p.field_off = 0;
-    p.dirty_off[0] = up256(rows * cols * 8);
-    p.dirty_off[1] = p.dirty_off[0] + up256(tiles * 4);
-    p.changed_off = p.dirty_off[1] + up256(tiles * 4);
-    p.status_off = p.changed_off + up256(MAX_GROUP * 4);
-    p.partial_off = p.status_off + up256(ST_WORDS * 8);
-    p.total = p.partial_off + up256((size_t)SNAP_BLOCKS * 4 * 8);
-    return p;
+Work carve(void *base, size_t rows, size_t cols) {
+    Carver c(base);
+    Work w = {};
+    w.tiles_x = (long)((cols + TW - 1) / TW);
+    w.tiles_y = (long)((rows + TH - 1) / TH);
+    const size_t tiles = (size_t)w.tiles_x * (size_t)w.tiles_y;
+    w.field = c.take<uint64_t>(rows * cols);
+    const size_t zero_from = c.at();
+    w.dirty[0] = c.take<int>(tiles);
+    w.dirty[1] = c.take<int>(tiles);
+    w.changed = c.take<int>(MAX_GROUP);
+    w.st = c.take<long long>(ST_WORDS);
+    w.zero_bytes = c.at() - zero_from;
+    w.partial = c.take<long long>((size_t)SNAP_BLOCKS * 4);
+    w.total = c.at();
+    return w;
 }
 
 // is a < b for two distances (a1, b1), (a2, b2) packed as above?  Exact.
@@ -325,7 +330,7 @@ extern "C" {
 
 size_t xrs_astar_workspace_bytes(int64_t rows, int64_t cols) {
     if (rows <= 0 || cols <= 0 || rows > XRS_ASTAR_MAX_CELLS || cols > XRS_ASTAR_MAX_CELLS || rows * cols > XRS_ASTAR_MAX_CELLS) return 0;
-    return plan((size_t)rows, (size_t)cols).total;
+    return carve(nullptr, (size_t)rows, (size_t)cols).total;
 }
 
 int xrs_astar(const void *data_dev, int dtype, int64_t rows, int64_t cols, int64_t start_row, int64_t start_col, int64_t goal_row,
@@ -350,28 +355,23 @@ int xrs_astar(const void *data_dev, int dtype, int64_t rows, int64_t cols, int64
 
     hipStream_t s = as_stream(stream);
     const long n = rows * cols;
-    const Plan pl = plan((size_t)rows, (size_t)cols);
-    const long tiles = pl.tiles_x * pl.tiles_y;
-    char *base = static_cast<char *>(work_dev);
-    uint64_t *field = (uint64_t *)(base + pl.field_off);
-    int *dirty[2] = {(int *)(base + pl.dirty_off[0]), (int *)(base + pl.dirty_off[1])};
-    int *changed = (int *)(base + pl.changed_off);
-    long long *st = (long long *)(base + pl.status_off), *partial = (long long *)(base + pl.partial_off);
-    XRS_HIP(hipMemsetAsync(base + pl.dirty_off[0], 0, pl.partial_off - pl.dirty_off[0], s));   // both dirty arrays, changed, status
+    const Work w = carve(work_dev, (size_t)rows, (size_t)cols);
+    const long tiles = w.tiles_x * w.tiles_y;
+    XRS_HIP(hipMemsetAsync(w.dirty[0], 0, w.zero_bytes, s));
 
     with_dtype_f32_last(dtype, [&](auto t) {   // (the code was checked above)
-        launch_init<dtype_of<decltype(t)>>(data_dev, n, barriers_dev, barriers_kind, n_barriers, field, out_dev, s);
+        launch_init<dtype_of<decltype(t)>>(data_dev, n, barriers_dev, barriers_kind, n_barriers, w.field, out_dev, s);
     });
     XRS_LAUNCH_CHECK();
     int n_partial = 0;
     if (snap_flags & (XRS_ASTAR_SNAP_START | XRS_ASTAR_SNAP_GOAL)) {
         n_partial = (int)((n + NT - 1) / NT < SNAP_BLOCKS ? (n + NT - 1) / NT : SNAP_BLOCKS);
-        hipLaunchKernelGGL(astar_snap_kernel, dim3((unsigned)n_partial), dim3(NT), 0, s, field, (long)rows, (long)cols, (long)start_row,
-                           (long)start_col, (long)goal_row, (long)goal_col, partial);
+        hipLaunchKernelGGL(astar_snap_kernel, dim3((unsigned)n_partial), dim3(NT), 0, s, w.field, (long)rows, (long)cols, (long)start_row,
+                           (long)start_col, (long)goal_row, (long)goal_col, w.partial);
         XRS_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(astar_setup_kernel, dim3(1), dim3(64), 0, s, field, (long)rows, (long)cols, (long)start_row, (long)start_col,
-                       (long)goal_row, (long)goal_col, snap_flags, partial, n_partial, pl.tiles_x, pl.tiles_y, dirty[0], st);
+    hipLaunchKernelGGL(astar_setup_kernel, dim3(1), dim3(64), 0, s, w.field, (long)rows, (long)cols, (long)start_row, (long)start_col,
+                       (long)goal_row, (long)goal_col, snap_flags, w.partial, n_partial, w.tiles_x, w.tiles_y, w.dirty[0], w.st);
     XRS_LAUNCH_CHECK();
 
     const long cap = n + 2;                              // Bellman-Ford: every pass but the last makes one more cell final
@@ -382,20 +382,20 @@ int xrs_astar(const void *data_dev, int dtype, int64_t rows, int64_t cols, int64
     while (!settled) {
         if (passes >= cap) return fail("xrs_astar: the distance field did not settle within %ld passes", cap);
         const int now = (int)(cap - passes < per_group ? cap - passes : per_group);
-        XRS_HIP(hipMemsetAsync(changed, 0, MAX_GROUP * 4, s));
+        XRS_HIP(hipMemsetAsync(w.changed, 0, MAX_GROUP * 4, s));
         for (int i = 0; i < now; ++i) {
             const long p = passes + i;
             if (connectivity == 8)
-                hipLaunchKernelGGL((astar_relax_kernel<true>), dim3((unsigned)tiles), dim3(NT), 0, s, field, (long)rows, (long)cols, pl.tiles_x,
-                                   pl.tiles_y, dirty[p & 1], dirty[(p + 1) & 1], changed + i,
-                                   (unsigned long long *)(st + ST_VISITS));
+                hipLaunchKernelGGL((astar_relax_kernel<true>), dim3((unsigned)tiles), dim3(NT), 0, s, w.field, (long)rows, (long)cols, w.tiles_x,
+                                   w.tiles_y, w.dirty[p & 1], w.dirty[(p + 1) & 1], w.changed + i,
+                                   (unsigned long long *)(w.st + ST_VISITS));
             else
-                hipLaunchKernelGGL((astar_relax_kernel<false>), dim3((unsigned)tiles), dim3(NT), 0, s, field, (long)rows, (long)cols, pl.tiles_x,
-                                   pl.tiles_y, dirty[p & 1], dirty[(p + 1) & 1], changed + i,
-                                   (unsigned long long *)(st + ST_VISITS));
+                hipLaunchKernelGGL((astar_relax_kernel<false>), dim3((unsigned)tiles), dim3(NT), 0, s, w.field, (long)rows, (long)cols, w.tiles_x,
+                                   w.tiles_y, w.dirty[p & 1], w.dirty[(p + 1) & 1], w.changed + i,
+                                   (unsigned long long *)(w.st + ST_VISITS));
             XRS_LAUNCH_CHECK();
         }
-        XRS_HIP(hipMemcpyAsync(seen, changed, now * 4, hipMemcpyDeviceToHost, s));
+        XRS_HIP(hipMemcpyAsync(seen, w.changed, now * 4, hipMemcpyDeviceToHost, s));
         XRS_HIP(hipStreamSynchronize(s));
         for (int i = 0; i < now && !settled; ++i) {
             ++passes;
@@ -404,12 +404,12 @@ int xrs_astar(const void *data_dev, int dtype, int64_t rows, int64_t cols, int64
     }
 
     if (!(snap_flags & XRS_ASTAR_NO_WALK)) {
-        if (connectivity == 8) hipLaunchKernelGGL((astar_walk_kernel<true>), dim3(1), dim3(64), 0, s, field, (long)rows, (long)cols, st, out_dev);
-        else hipLaunchKernelGGL((astar_walk_kernel<false>), dim3(1), dim3(64), 0, s, field, (long)rows, (long)cols, st, out_dev);
+        if (connectivity == 8) hipLaunchKernelGGL((astar_walk_kernel<true>), dim3(1), dim3(64), 0, s, w.field, (long)rows, (long)cols, w.st, out_dev);
+        else hipLaunchKernelGGL((astar_walk_kernel<false>), dim3(1), dim3(64), 0, s, w.field, (long)rows, (long)cols, w.st, out_dev);
         XRS_LAUNCH_CHECK();
     }
     long long host_st[ST_WORDS];
-    XRS_HIP(hipMemcpyAsync(host_st, st, sizeof host_st, hipMemcpyDeviceToHost, s));
+    XRS_HIP(hipMemcpyAsync(host_st, w.st, sizeof host_st, hipMemcpyDeviceToHost, s));
     XRS_HIP(hipStreamSynchronize(s));
     for (int i = 0; i < 7; ++i) status_host[i] = host_st[i];
     status_host[7] = passes;
@@ -420,9 +420,9 @@ int xrs_astar(const void *data_dev, int dtype, int64_t rows, int64_t cols, int64
 int xrs_astar_tile_visits(const void *work_dev, int64_t rows, int64_t cols, int64_t *visits_host, void *stream) {
     if (!work_dev || !visits_host) return fail("xrs_astar_tile_visits: null pointer");
     if (xrs_astar_workspace_bytes(rows, cols) == 0) return fail("xrs_astar_tile_visits: not the shape of a workspace");
-    const Plan pl = plan((size_t)rows, (size_t)cols);
+    const Work w = carve(const_cast<void *>(work_dev), (size_t)rows, (size_t)cols);
     long long v = 0;
-    XRS_HIP(hipMemcpyAsync(&v, static_cast<const char *>(work_dev) + pl.status_off + ST_VISITS * 8, 8, hipMemcpyDeviceToHost, as_stream(stream)));
+    XRS_HIP(hipMemcpyAsync(&v, w.st + ST_VISITS, 8, hipMemcpyDeviceToHost, as_stream(stream)));
     XRS_HIP(hipStreamSynchronize(as_stream(stream)));
     *visits_host = v;
     return 0;

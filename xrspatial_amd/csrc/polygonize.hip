@@ -29,6 +29,7 @@
 #include "xrs_common.h"
 #include "dtype_dispatch.h"
 #include "union_find.h"
+#include "workspace.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -433,63 +434,68 @@ __global__ void __launch_bounds__(THREADS) column_kernel(const U *__restrict__ i
 }
 
 // ------------------------------------------------------------------ workspaces
-inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-struct Plan {                                                     // of xrs_polygonize_census; the region plane comes first
-    size_t n, words, region_off, parent_off, mask_off, links_off, rootbits_off, cnt_off, sbits_off, scnt_off, cub_off,
-        cub_bytes, total;
+struct Work {                                                     // of xrs_polygonize_census; the region plane comes first
+    size_t n, words;
+    uint32_t *region, *parent, *cnt;                              // cnt[words], scnt[words]: the totals
+    uint8_t *mask, *links;
+    u64 *rootbits, *sbits, *scnt;
+    void *cub;
+    size_t cub_bytes, total;
 };
 
-Plan plan(uint64_t rows, uint64_t cols) {
-    Plan p{};
+Work carve(void *base, uint64_t rows, uint64_t cols) {
+    Carver c(base);
+    Work p{};
     p.n = rows * cols;
     p.words = (p.n + 63) / 64;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t at = off; off += up256(bytes); return at; };
-    p.region_off = take(p.n * 4);
-    p.parent_off = take(p.n * 4);
-    p.mask_off = take(p.n);
-    p.links_off = take(p.n);
-    p.rootbits_off = take(p.words * 8);
-    p.cnt_off = take((p.words + 1) * 4);
-    p.sbits_off = take(p.words * 32);
-    p.scnt_off = take((p.words + 1) * 8);
+    p.region = c.take<uint32_t>(p.n);
+    p.parent = c.take<uint32_t>(p.n);
+    p.mask = c.take<uint8_t>(p.n);
+    p.links = c.take<uint8_t>(p.n);
+    p.rootbits = c.take<u64>(p.words);
+    p.cnt = c.take<uint32_t>(p.words + 1);
+    p.sbits = c.take<u64>(p.words * 4);
+    p.scnt = c.take<u64>(p.words + 1);
     size_t a = 0, b = 0;
     (void)hipcub::DeviceScan::ExclusiveSum(nullptr, a, (uint32_t *)nullptr, (uint32_t *)nullptr, (size_t)(p.words + 1));
     (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, (u64 *)nullptr, (u64 *)nullptr, (size_t)(p.words + 1));
     p.cub_bytes = a > b ? a : b;
-    p.cub_off = take(p.cub_bytes > 0 ? p.cub_bytes : 1);
-    p.total = off;
+    p.cub = c.take<char>(p.cub_bytes > 0 ? p.cub_bytes : 1);
+    p.total = c.at();
     return p;
 }
 
-struct RingPlan {                                                 // of xrs_polygonize_rings
-    size_t n_states, max_rings, next_off, buf_off[4], lead_off, emit_off, keys_off[2], count1_off, ring_off_off, poly_off_off,
-        words_off, cub_off, cub_bytes, total;
+struct RingWork {                                                 // of xrs_polygonize_rings
+    size_t n_states, max_rings;
+    uint32_t *next, *buf[4], *lead, *words;
+    uint8_t *emit;
+    u64 *keys[2], *count1, *ring_off;
+    int64_t *poly_off;
+    void *cub;
+    size_t cub_bytes, total;
 };
 constexpr int WORD_RINGS = 0, WORD_CHANGED = 8, N_WORDS = 8 + 2 * MAX_ROUNDS + 8;
 
-RingPlan ring_plan(uint64_t n_states) {
-    RingPlan p{};
+RingWork carve_rings(void *base, uint64_t n_states) {
+    Carver c(base);
+    RingWork p{};
     p.n_states = n_states;
     p.max_rings = n_states / 4 + 1;                               // a ring has at least 4 states
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t at = off; off += up256(bytes); return at; };
-    p.next_off = take(n_states * 4);
-    for (int k = 0; k < 4; ++k) p.buf_off[k] = take(n_states * 4);
-    p.lead_off = take(n_states * 4);
-    p.emit_off = take(n_states);
-    for (int k = 0; k < 2; ++k) p.keys_off[k] = take(p.max_rings * 8);
-    p.count1_off = take((p.max_rings + 1) * 8);
-    p.ring_off_off = take((p.max_rings + 1) * 8);
-    p.poly_off_off = take((p.max_rings + 1) * 8);
-    p.words_off = take(N_WORDS * 4);
+    p.next = c.take<uint32_t>(n_states);
+    for (int k = 0; k < 4; ++k) p.buf[k] = c.take<uint32_t>(n_states);
+    p.lead = c.take<uint32_t>(n_states);
+    p.emit = c.take<uint8_t>(n_states);
+    for (int k = 0; k < 2; ++k) p.keys[k] = c.take<u64>(p.max_rings);
+    p.count1 = c.take<u64>(p.max_rings + 1);
+    p.ring_off = c.take<u64>(p.max_rings + 1);
+    p.poly_off = c.take<int64_t>(p.max_rings + 1);
+    p.words = c.take<uint32_t>(N_WORDS);
     size_t a = 0, b = 0;
     (void)hipcub::DeviceRadixSort::SortKeys(nullptr, a, (u64 *)nullptr, (u64 *)nullptr, (size_t)p.max_rings, 0, 64);
     (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, (u64 *)nullptr, (u64 *)nullptr, (size_t)(p.max_rings + 1));
     p.cub_bytes = a > b ? a : b;
-    p.cub_off = take(p.cub_bytes > 0 ? p.cub_bytes : 1);
-    p.total = off;
+    p.cub = c.take<char>(p.cub_bytes > 0 ? p.cub_bytes : 1);
+    p.total = c.at();
     return p;
 }
 
@@ -506,38 +512,33 @@ inline unsigned blocks_for(uint64_t n) { return (unsigned)((n + THREADS - 1) / T
 template <typename T>
 int census_impl(const T *in, const uint8_t *mask, int64_t rows, int64_t cols, int n8, void *work, uint64_t *n_regions,
                 uint64_t *n_states, hipStream_t s) {
-    const Plan p = plan(rows, cols);
-    char *base = (char *)work;
-    uint32_t *region = (uint32_t *)(base + p.region_off), *parent = (uint32_t *)(base + p.parent_off);
-    uint32_t *cnt = (uint32_t *)(base + p.cnt_off);
-    uint8_t *links = (uint8_t *)(base + p.links_off);
-    u64 *rootbits = (u64 *)(base + p.rootbits_off), *sbits = (u64 *)(base + p.sbits_off), *scnt = (u64 *)(base + p.scnt_off);
+    const Work p = carve(work, rows, cols);
     const Grid g{(uint32_t)rows, (uint32_t)cols, (uint32_t)((cols + TW - 1) / TW)};
     const size_t tiles = (size_t)g.tiles_x * ((rows + TH - 1) / TH);
     const unsigned cell_blocks = blocks_for(p.n);
-    XRS_HIP(hipMemsetAsync(cnt + p.words, 0, 4, s));
-    XRS_HIP(hipMemsetAsync(scnt + p.words, 0, 8, s));
+    XRS_HIP(hipMemsetAsync(p.cnt + p.words, 0, 4, s));
+    XRS_HIP(hipMemsetAsync(p.scnt + p.words, 0, 8, s));
     if (n8)
-        hipLaunchKernelGGL((link_kernel<T, true>), dim3((unsigned)tiles), dim3(THREADS), 0, s, in, mask, g, parent, links);
+        hipLaunchKernelGGL((link_kernel<T, true>), dim3((unsigned)tiles), dim3(THREADS), 0, s, in, mask, g, p.parent, p.links);
     else
-        hipLaunchKernelGGL((link_kernel<T, false>), dim3((unsigned)tiles), dim3(THREADS), 0, s, in, mask, g, parent, links);
+        hipLaunchKernelGGL((link_kernel<T, false>), dim3((unsigned)tiles), dim3(THREADS), 0, s, in, mask, g, p.parent, p.links);
     XRS_LAUNCH_CHECK();
-    hipLaunchKernelGGL(merge_kernel, dim3((unsigned)tiles), dim3(128), 0, s, links, g, parent);
+    hipLaunchKernelGGL(merge_kernel, dim3((unsigned)tiles), dim3(128), 0, s, p.links, g, p.parent);
     XRS_LAUNCH_CHECK();
-    hipLaunchKernelGGL(roots_kernel, dim3(cell_blocks), dim3(THREADS), 0, s, parent, mask, (uint64_t)p.n, rootbits, cnt);
+    hipLaunchKernelGGL(roots_kernel, dim3(cell_blocks), dim3(THREADS), 0, s, p.parent, mask, (uint64_t)p.n, p.rootbits, p.cnt);
     XRS_LAUNCH_CHECK();
     size_t cub_bytes = p.cub_bytes;
-    XRS_HIP(hipcub::DeviceScan::ExclusiveSum(base + p.cub_off, cub_bytes, cnt, cnt, (size_t)(p.words + 1), s));
-    hipLaunchKernelGGL(region_kernel, dim3(cell_blocks), dim3(THREADS), 0, s, parent, mask, (uint64_t)p.n, rootbits, cnt, region);
+    XRS_HIP(hipcub::DeviceScan::ExclusiveSum(p.cub, cub_bytes, p.cnt, p.cnt, (size_t)(p.words + 1), s));
+    hipLaunchKernelGGL(region_kernel, dim3(cell_blocks), dim3(THREADS), 0, s, p.parent, mask, (uint64_t)p.n, p.rootbits, p.cnt, p.region);
     XRS_LAUNCH_CHECK();
-    hipLaunchKernelGGL(census_kernel, dim3(cell_blocks), dim3(THREADS), 0, s, region, g, (uint64_t)p.n, sbits, scnt);
+    hipLaunchKernelGGL(census_kernel, dim3(cell_blocks), dim3(THREADS), 0, s, p.region, g, (uint64_t)p.n, p.sbits, p.scnt);
     XRS_LAUNCH_CHECK();
     cub_bytes = p.cub_bytes;
-    XRS_HIP(hipcub::DeviceScan::ExclusiveSum(base + p.cub_off, cub_bytes, scnt, scnt, (size_t)(p.words + 1), s));
+    XRS_HIP(hipcub::DeviceScan::ExclusiveSum(p.cub, cub_bytes, p.scnt, p.scnt, (size_t)(p.words + 1), s));
     uint32_t regions_total = 0;
     u64 states_total = 0;
-    XRS_HIP(hipMemcpyAsync(&regions_total, cnt + p.words, 4, hipMemcpyDeviceToHost, s));
-    XRS_HIP(hipMemcpyAsync(&states_total, scnt + p.words, 8, hipMemcpyDeviceToHost, s));
+    XRS_HIP(hipMemcpyAsync(&regions_total, p.cnt + p.words, 4, hipMemcpyDeviceToHost, s));
+    XRS_HIP(hipMemcpyAsync(&states_total, p.scnt + p.words, 8, hipMemcpyDeviceToHost, s));
     XRS_HIP(hipStreamSynchronize(s));
     *n_regions = regions_total;
     *n_states = states_total;
@@ -556,12 +557,12 @@ extern "C" {
 
 size_t xrs_polygonize_workspace_bytes(int64_t rows, int64_t cols) {
     if (rows < 1 || cols < 1 || (uint64_t)rows > 0xFFFFFFFFull / (uint64_t)cols) return 0;
-    return plan((uint64_t)rows, (uint64_t)cols).total;
+    return carve(nullptr, (uint64_t)rows, (uint64_t)cols).total;
 }
 
 size_t xrs_polygonize_rings_workspace_bytes(uint64_t n_states) {
     if (n_states == 0 || n_states > XRS_POLYGONIZE_MAX_STATES) return 0;
-    return ring_plan(n_states).total;
+    return carve_rings(nullptr, n_states).total;
 }
 
 int xrs_polygonize_census(const void *data_dev, int dtype, const void *mask_dev, int mask_dtype, int64_t rows, int64_t cols,
@@ -574,11 +575,11 @@ int xrs_polygonize_census(const void *data_dev, int dtype, const void *mask_dev,
     if (!data_dev || !work_dev || !n_regions || !n_states) return fail("xrs_polygonize_census: null pointer");
     *n_regions = *n_states = 0;
     hipStream_t s = as_stream(stream);
-    const Plan p = plan(rows, cols);
+    const Work p = carve(work_dev, rows, cols);
     uint8_t *mask = nullptr;
     int rc = 0;                                                   // (both codes were checked above)
     if (mask_dev) {
-        mask = (uint8_t *)work_dev + p.mask_off;
+        mask = p.mask;
         with_dtype(mask_dtype, [&](auto t) { rc = mask_impl((const dtype_of<decltype(t)> *)mask_dev, p.n, mask, s); });
         if (rc) return rc;
     }
@@ -598,72 +599,59 @@ int xrs_polygonize_rings(int64_t rows, int64_t cols, const void *work_dev, void 
     if (!work_dev || !rings_dev || !n_rings || !n_points) return fail("xrs_polygonize_rings: null pointer");
     *n_rings = *n_points = 0;
     hipStream_t s = as_stream(stream);
-    const Plan p = plan(rows, cols);
-    const RingPlan q = ring_plan(n_states);
+    const Work p = carve((void *)work_dev, rows, cols);
+    const RingWork q = carve_rings(rings_dev, n_states);
     if (n_regions == 0 || n_regions > q.max_rings) return fail("xrs_polygonize_rings: %llu regions do not fit %llu states",
                                                                (unsigned long long)n_regions, (unsigned long long)n_states);
-    const char *base = (const char *)work_dev;
-    char *rb = (char *)rings_dev;
-    const uint32_t *region = (const uint32_t *)(base + p.region_off);
-    const u64 *rootbits = (const u64 *)(base + p.rootbits_off), *sbits = (const u64 *)(base + p.sbits_off);
-    const u64 *spre = (const u64 *)(base + p.scnt_off);
-    uint32_t *next = (uint32_t *)(rb + q.next_off), *lead = (uint32_t *)(rb + q.lead_off);
-    uint32_t *buf[4];
-    for (int k = 0; k < 4; ++k) buf[k] = (uint32_t *)(rb + q.buf_off[k]);
-    uint8_t *emit = (uint8_t *)(rb + q.emit_off);
-    u64 *keys[2] = {(u64 *)(rb + q.keys_off[0]), (u64 *)(rb + q.keys_off[1])};
-    u64 *count1 = (u64 *)(rb + q.count1_off), *ring_off = (u64 *)(rb + q.ring_off_off);
-    int64_t *poly_off = (int64_t *)(rb + q.poly_off_off);
-    uint32_t *words = (uint32_t *)(rb + q.words_off);
     const Grid g{(uint32_t)rows, (uint32_t)cols, (uint32_t)((cols + TW - 1) / TW)};
     const unsigned cell_blocks = blocks_for(p.n), state_blocks = blocks_for(n_states);
     const uint32_t E = (uint32_t)n_states;
     uint32_t host_words[N_WORDS];
 
-    XRS_HIP(hipMemsetAsync(words, 0, N_WORDS * 4, s));
+    XRS_HIP(hipMemsetAsync(q.words, 0, N_WORDS * 4, s));
     // next -> `next`, key -> buf[2]
-    hipLaunchKernelGGL(succ_kernel, dim3(cell_blocks), dim3(THREADS), 0, s, region, g, (uint64_t)p.n, sbits, spre, rootbits, next,
-                       buf[2], emit);
+    hipLaunchKernelGGL(succ_kernel, dim3(cell_blocks), dim3(THREADS), 0, s, p.region, g, (uint64_t)p.n, p.sbits, p.scnt, p.rootbits, q.next,
+                       q.buf[2], q.emit);
     XRS_LAUNCH_CHECK();
 
     // leader: (next, key) double-buffered in (buf[0] | buf[1], buf[2] | buf[3]); round 0 reads `next` itself
-    const uint32_t *nin = next, *kin = buf[2];
+    const uint32_t *nin = q.next, *kin = q.buf[2];
     int done_rounds = 0, key_at = 2;
     bool settled = false;
     while (!settled && done_rounds < MAX_ROUNDS) {
         const int first = done_rounds;
         for (int k = 0; k < ROUND_GROUP && done_rounds < MAX_ROUNDS; ++k, ++done_rounds) {
-            uint32_t *nout = buf[done_rounds & 1], *kout = buf[2 + ((done_rounds + 1) & 1)];
+            uint32_t *nout = q.buf[done_rounds & 1], *kout = q.buf[2 + ((done_rounds + 1) & 1)];
             hipLaunchKernelGGL(leader_round, dim3(state_blocks), dim3(THREADS), 0, s, nin, kin, nout, kout, E,
-                               words + WORD_CHANGED + done_rounds);
+                               q.words + WORD_CHANGED + done_rounds);
             XRS_LAUNCH_CHECK();
             nin = nout, kin = kout, key_at = 2 + ((done_rounds + 1) & 1);
         }
-        XRS_HIP(hipMemcpyAsync(host_words, words, N_WORDS * 4, hipMemcpyDeviceToHost, s));
+        XRS_HIP(hipMemcpyAsync(host_words, q.words, N_WORDS * 4, hipMemcpyDeviceToHost, s));
         XRS_HIP(hipStreamSynchronize(s));
         for (int k = first; k < done_rounds; ++k) settled |= host_words[WORD_CHANGED + k] == 0;   // a still round: minima final
     }
     if (!settled) return fail("xrs_polygonize_rings: ring leaders did not settle in %d rounds", MAX_ROUNDS);
     if (rounds) rounds[0] = done_rounds;
-    hipLaunchKernelGGL(lead_kernel, dim3(state_blocks), dim3(THREADS), 0, s, (const uint32_t *)buf[key_at], lead, E);
+    hipLaunchKernelGGL(lead_kernel, dim3(state_blocks), dim3(THREADS), 0, s, (const uint32_t *)q.buf[key_at], q.lead, E);
     XRS_LAUNCH_CHECK();
 
     // rank: (nxt, val) double-buffered in (buf[0] | buf[1], buf[2] | buf[3])
-    hipLaunchKernelGGL(rank_init, dim3(state_blocks), dim3(THREADS), 0, s, (const uint32_t *)next, (const uint32_t *)lead,
-                       (const uint8_t *)emit, buf[0], buf[2], E);
+    hipLaunchKernelGGL(rank_init, dim3(state_blocks), dim3(THREADS), 0, s, (const uint32_t *)q.next, (const uint32_t *)q.lead,
+                       (const uint8_t *)q.emit, q.buf[0], q.buf[2], E);
     XRS_LAUNCH_CHECK();
     int rank_rounds = 0, at = 0;
     settled = false;
     while (!settled && rank_rounds < MAX_ROUNDS) {
         const int first = rank_rounds;
         for (int k = 0; k < ROUND_GROUP && rank_rounds < MAX_ROUNDS; ++k, ++rank_rounds) {
-            hipLaunchKernelGGL(rank_round, dim3(state_blocks), dim3(THREADS), 0, s, (const uint32_t *)buf[at],
-                               (const uint32_t *)buf[2 + at], buf[at ^ 1], buf[2 + (at ^ 1)], E,
-                               words + WORD_CHANGED + MAX_ROUNDS + rank_rounds);
+            hipLaunchKernelGGL(rank_round, dim3(state_blocks), dim3(THREADS), 0, s, (const uint32_t *)q.buf[at],
+                               (const uint32_t *)q.buf[2 + at], q.buf[at ^ 1], q.buf[2 + (at ^ 1)], E,
+                               q.words + WORD_CHANGED + MAX_ROUNDS + rank_rounds);
             XRS_LAUNCH_CHECK();
             at ^= 1;
         }
-        XRS_HIP(hipMemcpyAsync(host_words, words, N_WORDS * 4, hipMemcpyDeviceToHost, s));
+        XRS_HIP(hipMemcpyAsync(host_words, q.words, N_WORDS * 4, hipMemcpyDeviceToHost, s));
         XRS_HIP(hipStreamSynchronize(s));
         for (int k = first; k < rank_rounds; ++k) settled |= host_words[WORD_CHANGED + MAX_ROUNDS + k] == 0;
     }
@@ -673,27 +661,27 @@ int xrs_polygonize_rings(int64_t rows, int64_t cols, const void *work_dev, void 
     // are in buf[2], and buf[0] (list pointers, spent) is free for the ring index -- where xrs_polygonize_scatter looks
     static_assert(ROUND_GROUP % 2 == 0 && MAX_ROUNDS % ROUND_GROUP == 0, "the rank buffers' parity");
     if (at != 0) return fail("xrs_polygonize_rings: odd number of rank rounds");
-    const uint32_t *suffix = buf[2];                              // emitting states from each state to its ring's end
-    uint32_t *ring_of = buf[0];
+    const uint32_t *suffix = q.buf[2];                            // emitting states from each state to its ring's end
+    uint32_t *ring_of = q.buf[0];
 
-    hipLaunchKernelGGL(collect_kernel, dim3(cell_blocks), dim3(THREADS), 0, s, region, (uint64_t)p.n, sbits, spre,
-                       (const uint32_t *)lead, keys[0], words + WORD_RINGS, (uint32_t)q.max_rings);
+    hipLaunchKernelGGL(collect_kernel, dim3(cell_blocks), dim3(THREADS), 0, s, p.region, (uint64_t)p.n, p.sbits, p.scnt,
+                       (const uint32_t *)q.lead, q.keys[0], q.words + WORD_RINGS, (uint32_t)q.max_rings);
     XRS_LAUNCH_CHECK();
-    XRS_HIP(hipMemcpyAsync(host_words, words, 4, hipMemcpyDeviceToHost, s));
+    XRS_HIP(hipMemcpyAsync(host_words, q.words, 4, hipMemcpyDeviceToHost, s));
     XRS_HIP(hipStreamSynchronize(s));
     const uint32_t R = host_words[WORD_RINGS];
     if (R == 0 || R > q.max_rings || R < n_regions)
         return fail("xrs_polygonize_rings: %u rings for %llu states and %llu regions", R, (unsigned long long)n_states,
                     (unsigned long long)n_regions);
     size_t cub_bytes = q.cub_bytes;
-    XRS_HIP(hipcub::DeviceRadixSort::SortKeys(rb + q.cub_off, cub_bytes, (const u64 *)keys[0], keys[1], (size_t)R, 0, 64, s));
-    hipLaunchKernelGGL(ring_table_kernel, dim3(blocks_for((uint64_t)R + 1)), dim3(THREADS), 0, s, (const u64 *)keys[1], R, suffix,
-                       ring_of, count1, poly_off, (uint32_t)n_regions);
+    XRS_HIP(hipcub::DeviceRadixSort::SortKeys(q.cub, cub_bytes, (const u64 *)q.keys[0], q.keys[1], (size_t)R, 0, 64, s));
+    hipLaunchKernelGGL(ring_table_kernel, dim3(blocks_for((uint64_t)R + 1)), dim3(THREADS), 0, s, (const u64 *)q.keys[1], R, suffix,
+                       ring_of, q.count1, q.poly_off, (uint32_t)n_regions);
     XRS_LAUNCH_CHECK();
     cub_bytes = q.cub_bytes;
-    XRS_HIP(hipcub::DeviceScan::ExclusiveSum(rb + q.cub_off, cub_bytes, count1, ring_off, (size_t)R + 1, s));
+    XRS_HIP(hipcub::DeviceScan::ExclusiveSum(q.cub, cub_bytes, q.count1, q.ring_off, (size_t)R + 1, s));
     u64 total = 0;
-    XRS_HIP(hipMemcpyAsync(&total, ring_off + R, 8, hipMemcpyDeviceToHost, s));
+    XRS_HIP(hipMemcpyAsync(&total, q.ring_off + R, 8, hipMemcpyDeviceToHost, s));
     XRS_HIP(hipStreamSynchronize(s));
     *n_rings = R;
     *n_points = total;
@@ -708,21 +696,14 @@ int xrs_polygonize_scatter(const void *data_dev, int dtype, int64_t rows, int64_
     const int item = dtype_bytes(dtype);
     if (!item) return fail("xrs_polygonize_scatter: unsupported dtype code %d", dtype);
     if (n_states == 0 || n_states > XRS_POLYGONIZE_MAX_STATES) return fail("xrs_polygonize_scatter: bad state count");
-    const RingPlan q = ring_plan(n_states);
+    const RingWork q = carve_rings((void *)rings_dev, n_states);
     if (n_rings == 0 || n_rings > q.max_rings || n_regions == 0 || n_regions > n_rings)
         return fail("xrs_polygonize_scatter: bad ring or region count");
     if (!data_dev || !work_dev || !rings_dev || !points_dev || !ring_offsets_dev || !polygon_offsets_dev || !column_dev)
         return fail("xrs_polygonize_scatter: null pointer");
     hipStream_t s = as_stream(stream);
-    const Plan p = plan(rows, cols);
-    const char *base = (const char *)work_dev, *rb = (const char *)rings_dev;
-    const uint32_t *region = (const uint32_t *)(base + p.region_off);
-    const u64 *rootbits = (const u64 *)(base + p.rootbits_off), *sbits = (const u64 *)(base + p.sbits_off);
-    const u64 *spre = (const u64 *)(base + p.scnt_off);
-    const uint32_t *suffix = (const uint32_t *)(rb + q.buf_off[2]), *ring_of = (const uint32_t *)(rb + q.buf_off[0]);
-    const uint32_t *lead = (const uint32_t *)(rb + q.lead_off);
-    const uint8_t *emit = (const uint8_t *)(rb + q.emit_off);
-    const u64 *ring_off = (const u64 *)(rb + q.ring_off_off);
+    const Work p = carve((void *)work_dev, rows, cols);
+    const uint32_t *suffix = q.buf[2], *ring_of = q.buf[0];
     const Grid g{(uint32_t)rows, (uint32_t)cols, (uint32_t)((cols + TW - 1) / TW)};
     Affine tf{};
     if (transform_host) {
@@ -730,11 +711,11 @@ int xrs_polygonize_scatter(const void *data_dev, int dtype, int64_t rows, int64_
         tf.on = 1;
     }
     const unsigned cell_blocks = blocks_for(p.n);
-    hipLaunchKernelGGL(scatter_kernel, dim3(cell_blocks), dim3(THREADS), 0, s, g, (uint64_t)p.n, sbits, spre, lead, emit, suffix,
-                       ring_of, ring_off, tf, (double *)points_dev);
+    hipLaunchKernelGGL(scatter_kernel, dim3(cell_blocks), dim3(THREADS), 0, s, g, (uint64_t)p.n, p.sbits, p.scnt, q.lead, q.emit, suffix,
+                       ring_of, q.ring_off, tf, (double *)points_dev);
     XRS_LAUNCH_CHECK();
-#define XRS_POLY_COLUMN(U)                                                                                               \
-    hipLaunchKernelGGL(column_kernel<U>, dim3(cell_blocks), dim3(THREADS), 0, s, (const U *)data_dev, region, rootbits,  \
+#define XRS_POLY_COLUMN(U)                                                                                                   \
+    hipLaunchKernelGGL(column_kernel<U>, dim3(cell_blocks), dim3(THREADS), 0, s, (const U *)data_dev, p.region, p.rootbits,  \
                        (uint64_t)p.n, (U *)column_dev)
     if (item == 1) XRS_POLY_COLUMN(uint8_t);
     else if (item == 2) XRS_POLY_COLUMN(uint16_t);
@@ -742,8 +723,8 @@ int xrs_polygonize_scatter(const void *data_dev, int dtype, int64_t rows, int64_
     else XRS_POLY_COLUMN(u64);
 #undef XRS_POLY_COLUMN
     XRS_LAUNCH_CHECK();
-    XRS_HIP(hipMemcpyAsync(ring_offsets_dev, rb + q.ring_off_off, (n_rings + 1) * 8, hipMemcpyDeviceToDevice, s));
-    XRS_HIP(hipMemcpyAsync(polygon_offsets_dev, rb + q.poly_off_off, (n_regions + 1) * 8, hipMemcpyDeviceToDevice, s));
+    XRS_HIP(hipMemcpyAsync(ring_offsets_dev, q.ring_off, (n_rings + 1) * 8, hipMemcpyDeviceToDevice, s));
+    XRS_HIP(hipMemcpyAsync(polygon_offsets_dev, q.poly_off, (n_regions + 1) * 8, hipMemcpyDeviceToDevice, s));
     return 0;
 }
 

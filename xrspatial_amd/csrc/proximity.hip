@@ -25,12 +25,13 @@
 // Known limit: GREAT_CIRCLE does not extend (the device's sin / asin are not the reference's to the last bit, so a float32 tie
 // there is not the rule's tie anyway): proximity is unaffected, allocation / direction name the nearest of the float32-
 // equidistant targets of a row side where the rule may name another.
-// Workspace (ABI, include/xrs_hip.h): left | right | flag | list | count, each part rounded up to 256 bytes (plan()).
+// Workspace (ABI, include/xrs_hip.h): left | right | flag | list | count, each part rounded up to 256 bytes (carve()).
 // Contraction is off for the whole file: dx * dx + dy * dy must round as the reference's.
 #include "xrs_common.h"
 #include "dtype_dispatch.h"
 #include "value_match.h"
 #include "wave_reduce.h"
+#include "workspace.h"
 
 #include <cmath>
 #include <type_traits>
@@ -45,20 +46,20 @@ constexpr int SPAN = 256;                      // columns per scan step and per 
 constexpr int EUCLIDEAN = 0, GREAT_CIRCLE = 1, MANHATTAN = 2;
 constexpr int MODE_PROXIMITY = 0, MODE_ALLOCATION = 1, MODE_DIRECTION = 2, MODE_ALL = 3;
 
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-struct Plan {
-    size_t left_off, right_off, flag_off, list_off, count_off, total;
+struct Work {
+    int *left, *right, *flag, *list, *count;
+    size_t total;
 };
-Plan plan(size_t rows, size_t cols) {
-    Plan p;
-    p.left_off = 0;
-    p.right_off = up256(rows * cols * 4);
-    p.flag_off = p.right_off + up256(rows * cols * 4);
-    p.list_off = p.flag_off + up256(rows * 4);
-    p.count_off = p.list_off + up256(rows * 4);
-    p.total = p.count_off + 256;
-    return p;
+Work carve(void *base, size_t rows, size_t cols) {
+    Carver c(base);
+    Work w = {};
+    w.left = c.take<int>(rows * cols);
+    w.right = c.take<int>(rows * cols);
+    w.flag = c.take<int>(rows);
+    w.list = c.take<int>(rows);
+    w.count = c.take_bytes<int>(256);
+    w.total = c.at();
+    return w;
 }
 
 // rule 1: non-zero and finite, or equal to one of `values` under NumPy's == (64-bit integers as integers)
@@ -327,7 +328,7 @@ void launch_scan(const void *data, long rows, long cols, const void *values, int
 extern "C" {
 
 size_t xrs_proximity_workspace_bytes(int64_t rows, int64_t cols) {
-    return rows > 0 && cols > 0 ? plan((size_t)rows, (size_t)cols).total : 0;
+    return rows > 0 && cols > 0 ? carve(nullptr, (size_t)rows, (size_t)cols).total : 0;
 }
 
 int xrs_proximity(const void *data_dev, int dtype, int64_t rows, int64_t cols, const double *xs_dev, const double *ys_dev,
@@ -355,16 +356,13 @@ int xrs_proximity(const void *data_dev, int dtype, int64_t rows, int64_t cols, c
     if (max_distance != max_distance) return fail("xrs_proximity: max_distance is NaN");
 
     hipStream_t s = as_stream(stream);
-    const Plan pl = plan((size_t)rows, (size_t)cols);
-    char *base = static_cast<char *>(work_dev);
-    int *left = (int *)(base + pl.left_off), *right = (int *)(base + pl.right_off), *flag = (int *)(base + pl.flag_off);
-    int *list = (int *)(base + pl.list_off), *count = (int *)(base + pl.count_off);
+    const Work w = carve(work_dev, (size_t)rows, (size_t)cols);
     if (do_scan) {
         with_dtype_f32_last(dtype, [&](auto t) {   // (the code was checked above)
-            launch_scan<dtype_of<decltype(t)>>(data_dev, rows, cols, values_dev, values_kind, n_values, left, right, flag, s);
+            launch_scan<dtype_of<decltype(t)>>(data_dev, rows, cols, values_dev, values_kind, n_values, w.left, w.right, w.flag, s);
         });
         XRS_LAUNCH_CHECK();
-        hipLaunchKernelGGL(proximity_rows_kernel, dim3(1), dim3(SPAN), 0, s, flag, (long)rows, list, count);
+        hipLaunchKernelGGL(proximity_rows_kernel, dim3(1), dim3(SPAN), 0, s, w.flag, (long)rows, w.list, w.count);
         XRS_LAUNCH_CHECK();
     }
     if (do_search) {
@@ -372,7 +370,7 @@ int xrs_proximity(const void *data_dev, int dtype, int64_t rows, int64_t cols, c
         p.data = data_dev; p.dtype = dtype; p.rows = rows; p.cols = cols;
         p.xs = xs_dev; p.ys = ys_dev;
         p.lon = gc_dev; p.lat = gc_dev ? gc_dev + cols : nullptr; p.coslat = gc_dev ? gc_dev + cols + rows : nullptr;
-        p.left = left; p.right = right; p.list = list; p.count = count;
+        p.left = w.left; p.right = w.right; p.list = w.list; p.count = w.count;
         p.max2 = std::isinf(max_distance) ? INFINITY : max_distance * max_distance;
         p.mode = product; p.out = out_dev;
         const dim3 grid((unsigned)(rows * spans));

@@ -19,6 +19,7 @@
 #include "xrs_common.h"
 #include "dtype_dispatch.h"
 #include "union_find.h"
+#include "workspace.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -250,25 +251,25 @@ __global__ void __launch_bounds__(THREADS) label_kernel(const T *__restrict__ in
 }
 
 // ------------------------------------------------------------------ workspace
-struct Plan {
-    size_t words, parent_off, mask_off, cnt_off, cub_off, cub_bytes, total;
+struct Work {
+    uint32_t *parent, *cnt;         // cnt[words] is the total; after the scan cnt holds the prefix sums
+    unsigned long long *mask;
+    void *cub;
+    size_t words, cub_bytes, total;
 };
-
-inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-Plan plan(uint64_t rows, uint64_t cols) {
-    Plan p{};
+Work carve(void *base, uint64_t rows, uint64_t cols) {
+    Carver c(base);
+    Work w{};
     const uint64_t tiles_x = (cols + TW - 1) / TW;
-    p.words = rows * tiles_x;
-    p.parent_off = 0;
-    p.mask_off = up256(rows * cols * 4);
-    p.cnt_off = p.mask_off + up256(p.words * 8);
-    p.cub_off = p.cnt_off + up256((p.words + 1) * 4);
-    p.cub_bytes = 0;
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, p.cub_bytes, (uint32_t *)nullptr, (uint32_t *)nullptr,
-                                           (size_t)(p.words + 1));
-    p.total = p.cub_off + up256(p.cub_bytes > 0 ? p.cub_bytes : 1);
-    return p;
+    w.words = rows * tiles_x;
+    w.parent = c.take<uint32_t>(rows * cols);
+    w.mask = c.take<unsigned long long>(w.words);
+    w.cnt = c.take<uint32_t>(w.words + 1);
+    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, w.cub_bytes, (uint32_t *)nullptr, (uint32_t *)nullptr,
+                                           (size_t)(w.words + 1));
+    w.cub = c.take<char>(w.cub_bytes > 0 ? w.cub_bytes : 1);
+    w.total = c.at();
+    return w;
 }
 
 int check_args(const char *fn, const void *data_dev, int dtype, int64_t rows, int64_t cols, int neighborhood,
@@ -285,22 +286,19 @@ int check_args(const char *fn, const void *data_dev, int dtype, int64_t rows, in
 
 template <typename T>
 int link_impl(const T *in, int64_t rows, int64_t cols, int n8, void *work, uint64_t *n_new, hipStream_t s) {
-    const Plan p = plan(rows, cols);
-    char *base = (char *)work;
-    uint32_t *parent = (uint32_t *)(base + p.parent_off), *cnt = (uint32_t *)(base + p.cnt_off);
-    unsigned long long *mask = (unsigned long long *)(base + p.mask_off);
+    const Work w = carve(work, rows, cols);
     const Grid g{(uint32_t)rows, (uint32_t)cols, (uint32_t)((cols + TW - 1) / TW)};
     const size_t tiles = (size_t)g.tiles_x * ((rows + TH - 1) / TH);
-    XRS_HIP(hipMemsetAsync(cnt + p.words, 0, 4, s));
+    XRS_HIP(hipMemsetAsync(w.cnt + w.words, 0, 4, s));
     if (n8)
-        hipLaunchKernelGGL((link_kernel<T, true>), dim3((unsigned)tiles), dim3(THREADS), 0, s, in, g, parent, mask, cnt);
+        hipLaunchKernelGGL((link_kernel<T, true>), dim3((unsigned)tiles), dim3(THREADS), 0, s, in, g, w.parent, w.mask, w.cnt);
     else
-        hipLaunchKernelGGL((link_kernel<T, false>), dim3((unsigned)tiles), dim3(THREADS), 0, s, in, g, parent, mask, cnt);
+        hipLaunchKernelGGL((link_kernel<T, false>), dim3((unsigned)tiles), dim3(THREADS), 0, s, in, g, w.parent, w.mask, w.cnt);
     XRS_LAUNCH_CHECK();
-    size_t cub_bytes = p.cub_bytes;
-    XRS_HIP(hipcub::DeviceScan::ExclusiveSum(base + p.cub_off, cub_bytes, cnt, cnt, (size_t)(p.words + 1), s));
+    size_t cub_bytes = w.cub_bytes;
+    XRS_HIP(hipcub::DeviceScan::ExclusiveSum(w.cub, cub_bytes, w.cnt, w.cnt, (size_t)(w.words + 1), s));
     uint32_t total = 0;
-    XRS_HIP(hipMemcpyAsync(&total, cnt + p.words, 4, hipMemcpyDeviceToHost, s));
+    XRS_HIP(hipMemcpyAsync(&total, w.cnt + w.words, 4, hipMemcpyDeviceToHost, s));
     XRS_HIP(hipStreamSynchronize(s));
     *n_new = total;
     return 0;
@@ -308,20 +306,17 @@ int link_impl(const T *in, int64_t rows, int64_t cols, int n8, void *work, uint6
 
 template <typename T>
 int label_impl(const T *in, T *out, int64_t rows, int64_t cols, int n8, void *work, hipStream_t s) {
-    const Plan p = plan(rows, cols);
-    char *base = (char *)work;
-    uint32_t *parent = (uint32_t *)(base + p.parent_off), *pre = (uint32_t *)(base + p.cnt_off);
-    const unsigned long long *mask = (const unsigned long long *)(base + p.mask_off);
+    const Work w = carve(work, rows, cols);
     const Grid g{(uint32_t)rows, (uint32_t)cols, (uint32_t)((cols + TW - 1) / TW)};
     const size_t tiles = (size_t)g.tiles_x * ((rows + TH - 1) / TH);
     if (n8)
-        hipLaunchKernelGGL((merge_kernel<T, true>), dim3((unsigned)tiles), dim3(THREADS), 0, s, in, g, parent);
+        hipLaunchKernelGGL((merge_kernel<T, true>), dim3((unsigned)tiles), dim3(THREADS), 0, s, in, g, w.parent);
     else
-        hipLaunchKernelGGL((merge_kernel<T, false>), dim3((unsigned)tiles), dim3(THREADS), 0, s, in, g, parent);
+        hipLaunchKernelGGL((merge_kernel<T, false>), dim3((unsigned)tiles), dim3(THREADS), 0, s, in, g, w.parent);
     XRS_LAUNCH_CHECK();
     const uint64_t n = (uint64_t)rows * cols;
     hipLaunchKernelGGL(label_kernel<T>, dim3((unsigned)((n + THREADS - 1) / THREADS)), dim3(THREADS), 0, s, in, out, g,
-                       (uint32_t)n, parent, mask, pre);
+                       (uint32_t)n, w.parent, (const unsigned long long *)w.mask, w.cnt);
     XRS_LAUNCH_CHECK();
     return 0;
 }
@@ -332,7 +327,7 @@ extern "C" {
 
 size_t xrs_regions_workspace_bytes(int64_t rows, int64_t cols) {
     if (rows < 0 || cols < 0) return 0;
-    return plan((uint64_t)rows, (uint64_t)cols).total;
+    return carve(nullptr, (uint64_t)rows, (uint64_t)cols).total;
 }
 
 int xrs_regions_link(const void *data_dev, int dtype, int64_t rows, int64_t cols, int neighborhood, void *work_dev,

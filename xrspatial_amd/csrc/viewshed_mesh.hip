@@ -123,7 +123,7 @@ int viewshed_mesh_impl(const T *z, long rows, long cols, double scale, double zm
     if (tiles_x * tiles_y >= (1L << 31) || blocks_x * blocks_y >= (1L << 31))
         return fail("xrs_viewshed_mesh: raster too large for one call (%ld x %ld)", rows, cols);
     float *zv = static_cast<float *>(work);
-    float *bmax = reinterpret_cast<float *>(static_cast<char *>(work) + align256((size_t)rows * (size_t)cols * sizeof(float)));
+    float *bmax = reinterpret_cast<float *>(static_cast<char *>(work) + up256((size_t)rows * (size_t)cols * sizeof(float)));
     // the vertex heights as the kernels see them: float32 of the scaled bounds (the rounding is monotonic)
     const double vmin = (double)(float)(zmin * scale), vmax = (double)(float)(zmax * scale);
     hipLaunchKernelGGL((shadow_prepare_kernel<T>), dim3((unsigned)(blocks_x * blocks_y)), dim3(256), 0, s, z, rows, cols, scale, table_shift,

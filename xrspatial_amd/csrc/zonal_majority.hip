@@ -16,6 +16,7 @@
 // This is library-GEMM-style use of a vendor primitive for the sort only; every other step is a
 // hand-written kernel.  Workspace is caller-provided (xrs_zonal_majority_workspace_bytes).
 #include "xrs_common.h"
+#include "workspace.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -147,56 +148,59 @@ __global__ void backproject_kernel(const int32_t *zidx, long n, const double *ta
     for (int s = 0; s < n_stats; ++s) out[(long)s * n + i] = ok ? table[(long)s * nz + z] : nan("");
 }
 
-inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 template <typename VT>
-struct Plan {
+struct Work {
     using K = typename KeyOf<VT>::K;
-    size_t off_vk[2], off_zk[2], off_flags, off_pos, off_nruns, off_best, off_cub, cub_bytes, total;
-    Plan(long n, int nz) {
-        size_t o = 0;
-        for (int i = 0; i < 2; ++i) { off_vk[i] = o; o += up256((size_t)n * sizeof(K)); }
-        for (int i = 0; i < 2; ++i) { off_zk[i] = o; o += up256((size_t)n * 4); }
-        off_flags = o; o += up256((size_t)n);
-        off_pos = o; o += up256((size_t)n * 4);
-        off_nruns = o; o += 256;
-        off_best = o; o += up256((size_t)nz * 8);
-        size_t t1 = 0, t2 = 0, t3 = 0;
-        hipcub::DoubleBuffer<K> dk(nullptr, nullptr);
-        hipcub::DoubleBuffer<unsigned> dz(nullptr, nullptr);
-        (void)hipcub::DeviceRadixSort::SortPairs(nullptr, t1, dk, dz, (int)n);
-        (void)hipcub::DeviceRadixSort::SortPairs(nullptr, t2, dz, dk, (int)n);
-        (void)hipcub::DeviceSelect::Flagged(nullptr, t3, hipcub::CountingInputIterator<unsigned>(0), (unsigned char *)nullptr,
-                                      (unsigned *)nullptr, (unsigned *)nullptr, (int)n);
-        cub_bytes = up256(t1 > t2 ? (t1 > t3 ? t1 : t3) : (t2 > t3 ? t2 : t3)) + 256;
-        off_cub = o; o += cub_bytes;
-        total = o;
-    }
+    K *vk[2];
+    unsigned *zk[2], *pos, *nruns;
+    unsigned char *flags;
+    unsigned long long *best;
+    void *cub;
+    size_t cub_bytes, total;
 };
+template <typename VT>
+Work<VT> carve(void *base, long n, int nz) {
+    using K = typename KeyOf<VT>::K;
+    Carver c(base);
+    Work<VT> w = {};
+    for (int i = 0; i < 2; ++i) w.vk[i] = c.take<K>(n);
+    for (int i = 0; i < 2; ++i) w.zk[i] = c.take<unsigned>(n);
+    w.flags = c.take<unsigned char>(n);
+    w.pos = c.take<unsigned>(n);
+    w.nruns = c.take_bytes<unsigned>(256);
+    w.best = c.take<unsigned long long>(nz);
+    size_t t1 = 0, t2 = 0, t3 = 0;
+    hipcub::DoubleBuffer<K> dk(nullptr, nullptr);
+    hipcub::DoubleBuffer<unsigned> dz(nullptr, nullptr);
+    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, t1, dk, dz, (int)n);
+    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, t2, dz, dk, (int)n);
+    (void)hipcub::DeviceSelect::Flagged(nullptr, t3, hipcub::CountingInputIterator<unsigned>(0), (unsigned char *)nullptr,
+                                  (unsigned *)nullptr, (unsigned *)nullptr, (int)n);
+    w.cub_bytes = up256(t1 > t2 ? (t1 > t3 ? t1 : t3) : (t2 > t3 ? t2 : t3)) + 256;
+    w.cub = c.take_bytes(w.cub_bytes);
+    w.total = c.at();
+    return w;
+}
 
 // cells -> keys -> ordered by (zone, value); returns the sorted key arrays (inside `work`)
 template <typename VT, bool CANON>
 int sort_by_zone_value(const char *who, const int32_t *zidx, const VT *vals, long n, int nz, VT nodata, int has_nodata,
-                       void *work, size_t work_bytes, const Plan<VT> &pl, const unsigned **zs_out,
+                       void *work, size_t work_bytes, const Work<VT> &pl, const unsigned **zs_out,
                        const typename KeyOf<VT>::K **vs_out, hipStream_t s) {
     using K = typename KeyOf<VT>::K;
     if (!zidx || !vals || !work) return fail("%s: null pointer", who);
     if (work_bytes < pl.total) return fail("%s: workspace too small (%zu < %zu)", who, work_bytes, pl.total);
-    char *w = static_cast<char *>(work);
-    K *vk[2] = {reinterpret_cast<K *>(w + pl.off_vk[0]), reinterpret_cast<K *>(w + pl.off_vk[1])};
-    unsigned *zk[2] = {reinterpret_cast<unsigned *>(w + pl.off_zk[0]), reinterpret_cast<unsigned *>(w + pl.off_zk[1])};
-    void *cub = w + pl.off_cub;
     size_t cub_bytes = pl.cub_bytes;
     const unsigned grid_n = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL((make_keys_kernel<VT, CANON>), dim3(grid_n), dim3(256), 0, s, zidx, vals, n, nz, nodata, has_nodata, vk[0], zk[0]);
+    hipLaunchKernelGGL((make_keys_kernel<VT, CANON>), dim3(grid_n), dim3(256), 0, s, zidx, vals, n, nz, nodata, has_nodata, pl.vk[0], pl.zk[0]);
     XRS_LAUNCH_CHECK();
-    hipcub::DoubleBuffer<K> dk(vk[0], vk[1]);
-    hipcub::DoubleBuffer<unsigned> dz(zk[0], zk[1]);
-    XRS_HIP(hipcub::DeviceRadixSort::SortPairs(cub, cub_bytes, dk, dz, (int)n, 0, (int)sizeof(K) * 8, s));
+    hipcub::DoubleBuffer<K> dk(pl.vk[0], pl.vk[1]);
+    hipcub::DoubleBuffer<unsigned> dz(pl.zk[0], pl.zk[1]);
+    XRS_HIP(hipcub::DeviceRadixSort::SortPairs(pl.cub, cub_bytes, dk, dz, (int)n, 0, (int)sizeof(K) * 8, s));
     int zbits = 1;
     while ((1L << zbits) <= nz) ++zbits;
     cub_bytes = pl.cub_bytes;
-    XRS_HIP(hipcub::DeviceRadixSort::SortPairs(cub, cub_bytes, dz, dk, (int)n, 0, zbits, s));
+    XRS_HIP(hipcub::DeviceRadixSort::SortPairs(pl.cub, cub_bytes, dz, dk, (int)n, 0, zbits, s));
     *zs_out = dz.Current();
     *vs_out = dk.Current();
     return 0;
@@ -210,7 +214,7 @@ int majority_impl(const int32_t *zidx, const VT *vals, long n, int nz, VT nodata
     if (nz == 0) return 0;
     if (n >= (1L << 31)) return fail("xrs_zonal_majority: at most 2^31-1 cells per call");
     if (!majority) return fail("xrs_zonal_majority: null output");
-    Plan<VT> pl(n > 0 ? n : 1, nz);
+    const Work<VT> pl = carve<VT>(work, n > 0 ? n : 1, nz);
     if (n == 0) {                                   // no cells: every zone is NaN (all-ones is a quiet NaN)
         XRS_HIP(hipMemsetAsync(majority, 0xFF, (size_t)nz * sizeof(double), s));
         return 0;
@@ -220,23 +224,17 @@ int majority_impl(const int32_t *zidx, const VT *vals, long n, int nz, VT nodata
     if (int rc = sort_by_zone_value<VT, true>("xrs_zonal_majority", zidx, vals, n, nz, nodata, has_nodata, work, work_bytes,
                                               pl, &zs, &vs, s))
         return rc;
-    char *w = static_cast<char *>(work);
-    unsigned char *flags = reinterpret_cast<unsigned char *>(w + pl.off_flags);
-    unsigned *pos = reinterpret_cast<unsigned *>(w + pl.off_pos);
-    unsigned *nruns = reinterpret_cast<unsigned *>(w + pl.off_nruns);
-    unsigned long long *best = reinterpret_cast<unsigned long long *>(w + pl.off_best);
-    void *cub = w + pl.off_cub;
-    size_t cub_bytes = pl.cub_bytes;
     const unsigned grid_n = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL((head_flags_kernel<K>), dim3(grid_n), dim3(256), 0, s, zs, vs, n, flags);
+    hipLaunchKernelGGL((head_flags_kernel<K>), dim3(grid_n), dim3(256), 0, s, zs, vs, n, pl.flags);
     XRS_LAUNCH_CHECK();
-    cub_bytes = pl.cub_bytes;
-    XRS_HIP(hipcub::DeviceSelect::Flagged(cub, cub_bytes, hipcub::CountingInputIterator<unsigned>(0), flags, pos, nruns, (int)n, s));
-    XRS_HIP(hipMemsetAsync(best, 0, (size_t)nz * 8, s));
-    hipLaunchKernelGGL(vote_kernel, dim3((unsigned)((n + 256L * VOTE_PER - 1) / (256L * VOTE_PER))), dim3(256), 0, s, zs, pos,
-                       nruns, n, nz, best);
+    size_t cub_bytes = pl.cub_bytes;
+    XRS_HIP(hipcub::DeviceSelect::Flagged(pl.cub, cub_bytes, hipcub::CountingInputIterator<unsigned>(0), pl.flags, pl.pos, pl.nruns, (int)n,
+                                          s));
+    XRS_HIP(hipMemsetAsync(pl.best, 0, (size_t)nz * 8, s));
+    hipLaunchKernelGGL(vote_kernel, dim3((unsigned)((n + 256L * VOTE_PER - 1) / (256L * VOTE_PER))), dim3(256), 0, s, zs, pl.pos,
+                       pl.nruns, n, nz, pl.best);
     XRS_LAUNCH_CHECK();
-    hipLaunchKernelGGL((decode_kernel<VT>), dim3((nz + 255) / 256), dim3(256), 0, s, best, pos, vs, nz, majority);
+    hipLaunchKernelGGL((decode_kernel<VT>), dim3((nz + 255) / 256), dim3(256), 0, s, pl.best, pl.pos, vs, nz, majority);
     XRS_LAUNCH_CHECK();
     return 0;
 }
@@ -249,7 +247,7 @@ int group_impl(const int32_t *zidx, const VT *vals, long n, int nz, VT nodata, i
     if (n == 0) return 0;
     if (n >= (1L << 31)) return fail("xrs_zonal_group: at most 2^31-1 cells per call");
     if (!sorted) return fail("xrs_zonal_group: null output");
-    Plan<VT> pl(n, nz > 0 ? nz : 1);
+    const Work<VT> pl = carve<VT>(work, n, nz > 0 ? nz : 1);
     const unsigned *zs;
     const K *vs;
     if (int rc = sort_by_zone_value<VT, false>("xrs_zonal_group", zidx, vals, n, nz, nodata, has_nodata, work, work_bytes, pl,
@@ -278,7 +276,7 @@ int xrs_zonal_group_f64(const int32_t *zone_idx_dev, const double *values_dev, i
 
 size_t xrs_zonal_majority_workspace_bytes(int64_t n, int n_zones, int values_f64) {
     if (n <= 0 || n_zones <= 0) return 256;
-    return values_f64 ? Plan<double>(n, n_zones).total : Plan<float>(n, n_zones).total;
+    return values_f64 ? carve<double>(nullptr, n, n_zones).total : carve<float>(nullptr, n, n_zones).total;
 }
 
 int xrs_zonal_majority_f32(const int32_t *zone_idx_dev, const float *values_dev, int64_t n, int n_zones,

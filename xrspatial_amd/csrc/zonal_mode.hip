@@ -28,6 +28,7 @@
 // continuous data (where B is capped), but part_of is a multiplication by an odd number and can be inverted -- a few
 // thousand values picked to land in one part overflow a zone of 6000 cells (tests/zonal_majority_cases.py: keys_in_part).
 #include "xrs_common.h"
+#include "workspace.h"
 
 using namespace xrs;
 
@@ -624,40 +625,46 @@ __global__ void __launch_bounds__(64) reduce_kernel(const unsigned *__restrict__
     }
 }
 
-inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 template <typename VT>
-struct Plan {
+struct Work {
     using K = typename Key<VT>::K;
-    size_t off_hdr, off_zone_count, off_key_off, off_zone_cursor, off_part_base, off_chunk_base, off_zone_B, off_part_count,
-        off_part_off, off_part_cursor, off_best_count, off_best_key, off_keys, off_parted, off_chunk_zone, zero_bytes, total;
+    Hdr *hdr;
+    unsigned *zone_count, *part_count, *key_off, *zone_cursor, *part_base, *chunk_base, *part_off, *part_cursor, *best_count;
+    unsigned char *zone_B;
+    K *best_key, *keys, *parted;
+    unsigned short *chunk_zone;
+    size_t zero_bytes, total;
     long max_parts, max_chunks;
     bool direct;
-    Plan(long n, int nz) {
-        direct = n > ((long)PART_TARGET << LDS_B);
-        // sum over zones of 2^B <= 2 n / PART_TARGET + nz; of ceil(count / CHUNK) <= n / CHUNK + nz
-        max_parts = 2 * (n / PART_TARGET + 1) + nz;
-        max_chunks = ((n / CHUNK + 1 + nz + 7) / 8) * 8 + 8;          // (padded for xcd_tile's bands)
-        size_t o = 0;
-        off_hdr = o; o += 256;
-        off_zone_count = o; o += up256((size_t)nz * 4);
-        off_part_count = o; o += up256((size_t)max_parts * 4);
-        zero_bytes = o;                                               // [hdr, zone_count, part_count] are cleared per call
-        off_key_off = o; o += up256((size_t)(nz + 1) * 4);
-        off_zone_cursor = o; o += up256((size_t)nz * 4);
-        off_part_base = o; o += up256((size_t)(nz + 1) * 4);
-        off_chunk_base = o; o += up256((size_t)(nz + 1) * 4);
-        off_zone_B = o; o += up256((size_t)nz);
-        off_part_off = o; o += up256((size_t)max_parts * 4);
-        off_part_cursor = o; o += up256((size_t)max_parts * 4);
-        off_best_count = o; o += up256((size_t)max_parts * 4);
-        off_best_key = o; o += up256((size_t)max_parts * sizeof(K));
-        off_chunk_zone = o; o += up256((size_t)max_chunks * 2);
-        off_keys = o; o += up256((size_t)n * sizeof(K));
-        off_parted = o; o += up256((size_t)n * sizeof(K));
-        total = o;
-    }
 };
+template <typename VT>
+Work<VT> carve(void *base, long n, int nz) {
+    using K = typename Key<VT>::K;
+    Work<VT> w = {};
+    w.direct = n > ((long)PART_TARGET << LDS_B);
+    // sum over zones of 2^B <= 2 n / PART_TARGET + nz; of ceil(count / CHUNK) <= n / CHUNK + nz
+    w.max_parts = 2 * (n / PART_TARGET + 1) + nz;
+    w.max_chunks = ((n / CHUNK + 1 + nz + 7) / 8) * 8 + 8;            // (padded for xcd_tile's bands)
+    Carver c(base);
+    w.hdr = c.take_bytes<Hdr>(256);
+    w.zone_count = c.take<unsigned>(nz);
+    w.part_count = c.take<unsigned>(w.max_parts);
+    w.zero_bytes = c.at();                                            // [hdr, zone_count, part_count] are cleared per call
+    w.key_off = c.take<unsigned>(nz + 1);
+    w.zone_cursor = c.take<unsigned>(nz);
+    w.part_base = c.take<unsigned>(nz + 1);
+    w.chunk_base = c.take<unsigned>(nz + 1);
+    w.zone_B = c.take<unsigned char>(nz);
+    w.part_off = c.take<unsigned>(w.max_parts);
+    w.part_cursor = c.take<unsigned>(w.max_parts);
+    w.best_count = c.take<unsigned>(w.max_parts);
+    w.best_key = c.take<K>(w.max_parts);
+    w.chunk_zone = c.take<unsigned short>(w.max_chunks);
+    w.keys = c.take<K>(n);
+    w.parted = c.take<K>(n);
+    w.total = c.at();
+    return w;
+}
 
 template <typename VT>
 int mode_impl(const int32_t *zidx, const VT *vals, long n, int nz, VT nodata, int has_nodata, const uint32_t *counts_dev,
@@ -672,58 +679,48 @@ int mode_impl(const int32_t *zidx, const VT *vals, long n, int nz, VT nodata, in
         return 0;
     }
     if (n > 0 && (!zidx || !vals)) return fail("xrs_zonal_mode: null input");
-    Plan<VT> pl(n, nz);
+    const Work<VT> w = carve<VT>(work, n, nz);
     if (!work) return fail("xrs_zonal_mode: null workspace");
-    if (work_bytes < pl.total) return fail("xrs_zonal_mode: workspace too small (%zu < %zu)", work_bytes, pl.total);
-    char *w = static_cast<char *>(work);
-    Hdr *hdr = reinterpret_cast<Hdr *>(w + pl.off_hdr);
-    auto u32 = [&](size_t off) { return reinterpret_cast<unsigned *>(w + off); };
-    unsigned *zone_count = u32(pl.off_zone_count), *key_off = u32(pl.off_key_off), *zone_cursor = u32(pl.off_zone_cursor),
-             *part_base = u32(pl.off_part_base), *chunk_base = u32(pl.off_chunk_base), *part_count = u32(pl.off_part_count),
-             *part_off = u32(pl.off_part_off), *part_cursor = u32(pl.off_part_cursor), *best_count = u32(pl.off_best_count);
-    unsigned char *zone_B = reinterpret_cast<unsigned char *>(w + pl.off_zone_B);
-    unsigned short *chunk_zone = reinterpret_cast<unsigned short *>(w + pl.off_chunk_zone);
-    K *best_key = reinterpret_cast<K *>(w + pl.off_best_key), *keys = reinterpret_cast<K *>(w + pl.off_keys),
-      *parted = reinterpret_cast<K *>(w + pl.off_parted);
-    XRS_HIP(hipMemsetAsync(w, 0, pl.zero_bytes, s));
+    if (work_bytes < w.total) return fail("xrs_zonal_mode: workspace too small (%zu < %zu)", work_bytes, w.total);
+    XRS_HIP(hipMemsetAsync(w.hdr, 0, w.zero_bytes, s));
     const size_t zone_lds = (size_t)nz * 4;
     const long n_tiles = (n + TILE - 1) / TILE;
     if (counts_dev) {
         // the caller has them (the partial-sums reduction counts the same cells): one pass over the rasters saved
-        XRS_HIP(hipMemcpyAsync(zone_count, counts_dev, (size_t)nz * 4, hipMemcpyDeviceToDevice, s));
+        XRS_HIP(hipMemcpyAsync(w.zone_count, counts_dev, (size_t)nz * 4, hipMemcpyDeviceToDevice, s));
     } else if (n_tiles) {
         const unsigned g1 = (unsigned)(n_tiles < 4096 ? n_tiles : 4096);
         hipLaunchKernelGGL((zone_count_kernel<VT>), dim3(g1), dim3(TILE_THREADS), zone_lds, s, zidx, vals, n, nz, nodata, has_nodata,
-                           zone_count);
+                           w.zone_count);
         XRS_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(plan_kernel, dim3(1), dim3(1024), 0, s, zone_count, nz, key_off, zone_cursor, part_base, chunk_base, zone_B,
-                       part_count, part_off, hdr);
+    hipLaunchKernelGGL(plan_kernel, dim3(1), dim3(1024), 0, s, w.zone_count, nz, w.key_off, w.zone_cursor, w.part_base, w.chunk_base, w.zone_B,
+                       w.part_count, w.part_off, w.hdr);
     XRS_LAUNCH_CHECK();
-    hipLaunchKernelGGL(chunk_table_kernel, dim3(nz), dim3(256), 0, s, chunk_base, nz, chunk_zone);
+    hipLaunchKernelGGL(chunk_table_kernel, dim3(nz), dim3(256), 0, s, w.chunk_base, nz, w.chunk_zone);
     XRS_LAUNCH_CHECK();
     if (n_tiles) {
         hipLaunchKernelGGL((scatter_zone_kernel<VT>), dim3((unsigned)n_tiles), dim3(TILE_THREADS), zone_lds, s, zidx, vals, n, nz, nodata,
-                           has_nodata, zone_cursor, keys);
+                           has_nodata, w.zone_cursor, w.keys);
         XRS_LAUNCH_CHECK();
-        hipLaunchKernelGGL((part_hist_kernel<K, false>), dim3((unsigned)pl.max_chunks), dim3(CHUNK_THREADS), 0, s, keys, key_off,
-                           part_base, chunk_base, chunk_zone, zone_B, nz, hdr, part_count);
+        hipLaunchKernelGGL((part_hist_kernel<K, false>), dim3((unsigned)w.max_chunks), dim3(CHUNK_THREADS), 0, s, w.keys, w.key_off,
+                           w.part_base, w.chunk_base, w.chunk_zone, w.zone_B, nz, w.hdr, w.part_count);
         XRS_LAUNCH_CHECK();
-        if (pl.direct) {                           // only a raster large enough to hold a zone of more than 2^LDS_B parts
-            hipLaunchKernelGGL((part_hist_kernel<K, true>), dim3((unsigned)pl.max_chunks), dim3(CHUNK_THREADS), 0, s, keys, key_off,
-                               part_base, chunk_base, chunk_zone, zone_B, nz, hdr, part_count);
+        if (w.direct) {                           // only a raster large enough to hold a zone of more than 2^LDS_B parts
+            hipLaunchKernelGGL((part_hist_kernel<K, true>), dim3((unsigned)w.max_chunks), dim3(CHUNK_THREADS), 0, s, w.keys, w.key_off,
+                               w.part_base, w.chunk_base, w.chunk_zone, w.zone_B, nz, w.hdr, w.part_count);
             XRS_LAUNCH_CHECK();
         }
     }
-    hipLaunchKernelGGL(part_offsets_kernel, dim3(nz), dim3(256), 0, s, part_count, key_off, part_base, zone_B, nz, part_off, part_cursor);
+    hipLaunchKernelGGL(part_offsets_kernel, dim3(nz), dim3(256), 0, s, w.part_count, w.key_off, w.part_base, w.zone_B, nz, w.part_off, w.part_cursor);
     XRS_LAUNCH_CHECK();
     if (n_tiles) {
-        hipLaunchKernelGGL((scatter_part_kernel<K, false>), dim3((unsigned)pl.max_chunks), dim3(CHUNK_THREADS), 0, s, keys, key_off,
-                           part_base, chunk_base, chunk_zone, zone_B, nz, hdr, part_cursor, parted);
+        hipLaunchKernelGGL((scatter_part_kernel<K, false>), dim3((unsigned)w.max_chunks), dim3(CHUNK_THREADS), 0, s, w.keys, w.key_off,
+                           w.part_base, w.chunk_base, w.chunk_zone, w.zone_B, nz, w.hdr, w.part_cursor, w.parted);
         XRS_LAUNCH_CHECK();
-        if (pl.direct) {
-            hipLaunchKernelGGL((scatter_part_kernel<K, true>), dim3((unsigned)pl.max_chunks), dim3(CHUNK_THREADS), 0, s, keys, key_off,
-                               part_base, chunk_base, chunk_zone, zone_B, nz, hdr, part_cursor, parted);
+        if (w.direct) {
+            hipLaunchKernelGGL((scatter_part_kernel<K, true>), dim3((unsigned)w.max_chunks), dim3(CHUNK_THREADS), 0, s, w.keys, w.key_off,
+                               w.part_base, w.chunk_base, w.chunk_zone, w.zone_B, nz, w.hdr, w.part_cursor, w.parted);
             XRS_LAUNCH_CHECK();
         }
     }
@@ -732,11 +729,11 @@ int mode_impl(const int32_t *zidx, const VT *vals, long n, int nz, VT nodata, in
         long per_cu = 160 * 1024 / (SLOTS * (long)(sizeof(K) + 8) + 2304);
         if (per_cu > 8) per_cu = 8;                 // (2048 threads per CU)
         const long slots = ((long)cus * per_cu - 1) | 1;
-        hipLaunchKernelGGL((count_kernel<K>), dim3((unsigned)(slots < pl.max_parts ? slots : pl.max_parts)), dim3(256), 0, s, keys, parted,
-                           part_off, part_count, hdr, best_count, best_key);
+        hipLaunchKernelGGL((count_kernel<K>), dim3((unsigned)(slots < w.max_parts ? slots : w.max_parts)), dim3(256), 0, s, w.keys, w.parted,
+                           w.part_off, w.part_count, w.hdr, w.best_count, w.best_key);
     }
     XRS_LAUNCH_CHECK();
-    hipLaunchKernelGGL((reduce_kernel<VT>), dim3(nz), dim3(64), 0, s, best_count, best_key, part_base, nz, hdr, majority);
+    hipLaunchKernelGGL((reduce_kernel<VT>), dim3(nz), dim3(64), 0, s, w.best_count, w.best_key, w.part_base, nz, w.hdr, majority);
     XRS_LAUNCH_CHECK();
     return 0;
 }
@@ -747,7 +744,7 @@ extern "C" {
 
 size_t xrs_zonal_mode_workspace_bytes(int64_t n, int n_zones, int values_f64) {
     if (n < 0 || n_zones <= 0) return 256;
-    return values_f64 ? Plan<double>(n, n_zones).total : Plan<float>(n, n_zones).total;
+    return values_f64 ? carve<double>(nullptr, n, n_zones).total : carve<float>(nullptr, n, n_zones).total;
 }
 
 int xrs_zonal_mode_max_zones(void) { return MAX_ZONES; }
