@@ -777,6 +777,36 @@ int xrs_flow_flats_workspace_size(int64_t rows, int64_t cols, uint64_t *bytes_ou
 int xrs_flow_flats(const void *z_dev, int dtype, int64_t rows, int64_t cols, float *code_dev, void *work_dev, int64_t *status_host,
                    int flags, void *stream);
 
+/* Accumulated least cost from a set of sources over a friction surface (no reference counterpart; the rule:
+ * xrspatial_amd/cost_distance.py).
+ *   xrs_cost_distance  raster_dev (`dtype`: any XRS_DT_* code) says where the sources are: a source is a cell that is a target
+ *              by xrs_proximity's rule (values_dev / values_kind / n_values as there: non-zero and finite with n_values == 0)
+ *              and passable.  friction_dev (`friction_dtype`: XRS_DT_F32 or XRS_DT_F64): a cell is passable when its friction
+ *              is finite and > 0.  A step between two passable neighbours u, v costs
+ *              L * ((float64(f(u)) + float64(f(v))) * 0.5), L = cellsize_x (E, W), cellsize_y (N, S) or diag (the caller's
+ *              sqrt(cx^2 + cy^2); only with connectivity 8): one IEEE add, two multiplies.  dist_dev (float64) = the least
+ *              plane D with D = 0 at sources and D(v) = min over u of fl(D(u) + w(u, v)), NaN where the cell is impassable,
+ *              unreached or D > max_cost.  backlink_dev (float32, or NULL): 0 at sources, NaN where dist_dev is NaN, else the
+ *              ESRI code (xrs_flow_direction's) of the first neighbour n with D(n) < D(c) and fl(D(n) + w(n, c)) == D(c).
+ *              The plane is relaxed by xrs_fill's schedule (tiles of XRS_FILL_TILE cells square in LDS, 2 x 2 colours, rounds;
+ *              the call waits for the stream once a round and at its end).  The result planes are other planes than the inputs.
+ *   work_dev   caller-owned; xrs_cost_distance_workspace_size writes its bytes to *bytes_out (0 for an empty raster or one
+ *              beyond XRS_FLOW_MAX_CELLS cells) and returns 0, or non-zero for a null pointer.
+ *   status_host HOST array of XRS_COST_STATUS_WORDS words, laid out as xrs_fill's: [0] rounds run; [1] tiles launched in all;
+ *              [2], [3] nanoseconds of the first launch and of the last two; [4] sources; [5] absorbed cells (reached, no source,
+ *              and no neighbour fits the back-link rule: a step was lost to rounding); [6] cells reached, the sources included;
+ *              per round k the words [8 + k], [8 + ROUNDS + k], [8 + 2 ROUNDS + k] of xrs_fill.  Times only with XRS_COST_TIMED.
+ *   xrs_cost_allocation  out_dev (float32) = float32(raster[b]) where basins_dev (float64: xrs_flow_accumulate's basins of the
+ *              back-link plane, the linear index of the source a cell's chain ends in) holds b, NaN where it holds NaN.  One launch. */
+enum { XRS_COST_TIMED = 1, XRS_COST_STATUS_WORDS = 256 };
+int xrs_cost_distance_workspace_size(int64_t rows, int64_t cols, uint64_t *bytes_out);
+int xrs_cost_distance(const void *raster_dev, int dtype, const void *values_dev, int values_kind, int n_values, const void *friction_dev,
+                      int friction_dtype, int64_t rows, int64_t cols, double cellsize_x, double cellsize_y, double diag, double max_cost,
+                      int connectivity, double *dist_dev, float *backlink_dev, void *work_dev, int64_t *status_host, int flags,
+                      void *stream);
+int xrs_cost_allocation(const double *basins_dev, const void *raster_dev, int dtype, int64_t rows, int64_t cols, float *out_dev,
+                        void *stream);
+
 /* multispectral.true_color (xrspatial/multispectral.py:1334-1495).
  *   xrs_nan_minmax_f32: minmax_dev[0..1] = np.nanmin / np.nanmax of a float32 plane (NaN, NaN if it holds no number);
  *   xrs_true_color_u8:  rgba[i] = { stretch(red), stretch(green), stretch(blue), alpha } with

@@ -4,7 +4,7 @@ Drop-in for the `xrspatial.*` functions on that path (same names, signatures, Da
 in/out): slope, aspect, hillshade, curvature, focal.mean / apply / focal_stats,
 convolution.convolve_2d / convolution_2d, multispectral ndvi / evi / savi (+ nbr, nbr2, ndmi),
 zonal.stats, zonal.regions, classify (binary, reclassify, equal_interval, quantile, percentiles, box_plot, std_mean,
-head_tail_breaks, maximum_breaks), natural_breaks, perlin, generate_terrain, bump, viewshed (the sweep and the ray-traced mesh variant), proximity / allocation / direction, a_star_search, fill / flow_direction / flow_accumulation / basins (D8 hydrology with depression fill and flat resolution), local (cell_stats, combine, the frequencies, positions, rank, popularity),
+head_tail_breaks, maximum_breaks), natural_breaks, perlin, generate_terrain, bump, viewshed (the sweep and the ray-traced mesh variant), proximity / allocation / direction, a_star_search, cost_distance / cost_allocation / cost_backlink (least accumulated cost over a friction surface), fill / flow_direction / flow_accumulation / basins (D8 hydrology with depression fill and flat resolution), local (cell_stats, combine, the frequencies, positions, rank, popularity),
 experimental.polygonize.  Python host code calling hand-written HIP kernels through the C ABI of
 libxrs_hip.so (include/xrs_hip.h); no PyTorch, CuPy, Numba or Triton involved.
 
@@ -22,6 +22,7 @@ from .aspect import aspect  # noqa: F401
 from .bump import bump  # noqa: F401
 from .classify import (binary, box_plot, equal_interval, head_tail_breaks, maximum_breaks, percentiles,  # noqa: F401
                        quantile, reclassify, std_mean)
+from .cost_distance import cost_allocation, cost_backlink, cost_distance  # noqa: F401
 from .curvature import curvature  # noqa: F401
 from .focal import mean  # noqa: F401
 from .fused import fuse  # noqa: F401

@@ -229,6 +229,10 @@ _PROTOTYPES = {
     "xrs_fill": [c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, ctypes.POINTER(c_int64), c_int, c_void_p],
     "xrs_flow_flats_workspace_size": [c_int64, c_int64, ctypes.POINTER(ctypes.c_uint64)],
     "xrs_flow_flats": [c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, ctypes.POINTER(c_int64), c_int, c_void_p],
+    "xrs_cost_distance_workspace_size": [c_int64, c_int64, ctypes.POINTER(ctypes.c_uint64)],
+    "xrs_cost_distance": [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int64, c_int64, c_double, c_double, c_double,
+                          c_double, c_int, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int64), c_int, c_void_p],
+    "xrs_cost_allocation": [c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p],
     "xrs_comm_unique_id": [c_void_p],
     "xrs_comm_init_rank": [ctypes.POINTER(c_void_p), c_void_p, c_int, c_int],
     "xrs_comm_destroy": [c_void_p],

@@ -25,9 +25,9 @@
 //            No loop depends on the data without a bound, nothing waits on another block.
 #include "xrs_common.h"
 #include "dtype_dispatch.h"
+#include "tile_rounds.h"
 #include "workspace.h"
 
-#include <chrono>
 #include <cmath>
 
 #pragma clang fp contract(off)
@@ -36,20 +36,7 @@ using namespace xrs;
 
 namespace {
 
-constexpr int TILE = XRS_FILL_TILE;             // 64
-constexpr int THREADS = 256;                    // four waves
-constexpr int STRIP = TILE / 4;                 // rows of a thread's strip
-constexpr int LD = TILE + 2;                    // lanes read adjacent words of a row: no bank conflict at any pitch
-constexpr int HALO = 4 * TILE + 4;
-constexpr int CAP = 128;                        // in-tile iterations per launch
 constexpr unsigned INF = 0xffffffffu;           // "no drained cell of this elevation reached"
-constexpr int SLOTS = 64, SLOT_STRIDE = 64;
-constexpr int TOTAL_WORD = SLOTS * SLOT_STRIDE; // the round's fallen cells, then the four list lengths of the next round
-constexpr int COUNT_WORD = TOTAL_WORD + 1;
-constexpr int HEAD_WORDS = TOTAL_WORD + 64;
-constexpr int ROUNDS_KEPT = XRS_FILL_STATUS_ROUNDS;
-static_assert(TILE == 64 && STRIP == 16, "a wave's lanes are a tile's columns");
-static_assert(8 + 3 * ROUNDS_KEPT <= XRS_FILL_STATUS_WORDS, "status layout");
 
 template <typename T>
 __device__ __forceinline__ T nan_of() { return (T)nan_f32(); }
@@ -207,26 +194,6 @@ __global__ void __launch_bounds__(THREADS) relax_kernel(const typename Op::Z *__
     }
 }
 
-struct Offsets {
-    unsigned at[4];
-};
-
-// the flags of this round -> the four tile lists of the next one; the round's total
-__global__ void __launch_bounds__(THREADS) next_lists_kernel(unsigned tiles, unsigned tiles_x, unsigned *__restrict__ flags,
-                                                             unsigned *__restrict__ list, Offsets off, unsigned *__restrict__ head) {
-    const unsigned tile = blockIdx.x * THREADS + threadIdx.x;
-    if (tile < tiles && flags[tile] != 0u) {
-        flags[tile] = 0u;
-        const unsigned ti = tile / tiles_x, tj = tile - ti * tiles_x;
-        const unsigned c = ((ti & 1u) << 1) | (tj & 1u);
-        list[off.at[c] + atomicAdd(head + COUNT_WORD + c, 1u)] = tile;
-    }
-    if (blockIdx.x == 0 && threadIdx.x < SLOTS) {
-        const unsigned v = head[threadIdx.x * SLOT_STRIDE];
-        if (v != 0u) atomicAdd(head + TOTAL_WORD, v);
-    }
-}
-
 // ------------------------------------------------------------------ first and last launches
 template <typename T>
 __device__ __forceinline__ bool rim_cell(const T *__restrict__ z, long i, long j, long rows, long cols) {
@@ -286,73 +253,29 @@ __global__ void __launch_bounds__(THREADS) flat_codes_kernel(const T *__restrict
     code[u] = (float)c;
 }
 
-inline int64_t now_ns() {
-    return std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
 struct Work {
-    unsigned *head, *flags, *list, *d;
+    RoundWork rounds;
+    unsigned *d;
     size_t total;
 };
 Work carve(void *base, size_t rows, size_t cols, bool with_d) {
-    const size_t tiles = ((rows + TILE - 1) / TILE) * ((cols + TILE - 1) / TILE);
     Carver c(base);
     Work w = {};
-    w.head = c.take<unsigned>(HEAD_WORDS);
-    w.flags = c.take<unsigned>(tiles);
-    w.list = c.take<unsigned>(tiles);
+    w.rounds = carve_rounds(c, rows, cols);
     if (with_d) w.d = c.take<unsigned>(rows * cols);
     w.total = c.at();
     return w;
 }
 
-// the rounds: status words 0 (rounds run), 1 (tiles launched), 8 + k, 8 + KEPT + k, 8 + 2 KEPT + k (fallen cells, tiles, ns)
+// the rounds of tile_rounds.h with relax_kernel<Op> as the launch of a colour
 template <typename Op>
 int run_rounds(const char *what, const typename Op::Z *z, typename Op::V *plane, long rows, long cols, const Work &wk, int64_t *status,
                bool timed, hipStream_t s) {
-    const unsigned tiles_y = (unsigned)((rows + TILE - 1) / TILE), tiles_x = (unsigned)((cols + TILE - 1) / TILE);
-    const unsigned tiles = tiles_y * tiles_x;                            // at most 2^26: a row or a column of tiles of one cell each
-    const unsigned ny[2] = {(tiles_y + 1) / 2, tiles_y / 2}, nx[2] = {(tiles_x + 1) / 2, tiles_x / 2};
-    unsigned count[4];
-    Offsets off;
-    for (unsigned c = 0, at = 0; c < 4; ++c) {
-        count[c] = ny[c >> 1] * nx[c & 1];
-        off.at[c] = at;
-        at += count[c];
-    }
-    const uint64_t bound = (uint64_t)rows * (uint64_t)cols + 1;          // a round that moves anything brings one more cell to its last value
-    XRS_HIP(hipMemsetAsync(wk.flags, 0, (size_t)tiles * 4, s));
-    int64_t launched_all = 0;
-    for (uint64_t round = 0;; ++round) {
-        int64_t t0 = 0;
-        if (timed) { XRS_HIP(hipStreamSynchronize(s)); t0 = now_ns(); }
-        XRS_HIP(hipMemsetAsync(wk.head, 0, (size_t)HEAD_WORDS * 4, s));
-        int64_t launched = 0;
-        for (int c = 0; c < 4; ++c) {
-            if (!count[c]) continue;
-            hipLaunchKernelGGL((relax_kernel<Op>), dim3(count[c]), dim3(THREADS), 0, s, z, plane, rows, cols, tiles_y, tiles_x, c, nx[c & 1],
-                               round ? wk.list + off.at[c] : (const unsigned *)nullptr, wk.flags, wk.head);
-            XRS_LAUNCH_CHECK();
-            launched += count[c];
-        }
-        hipLaunchKernelGGL(next_lists_kernel, dim3((tiles + THREADS - 1) / THREADS), dim3(THREADS), 0, s, tiles, tiles_x, wk.flags, wk.list, off,
-                           wk.head);
-        XRS_LAUNCH_CHECK();
-        unsigned words[5] = {0, 0, 0, 0, 0};
-        XRS_HIP(hipMemcpyAsync(words, wk.head + TOTAL_WORD, sizeof(words), hipMemcpyDeviceToHost, s));
-        XRS_HIP(hipStreamSynchronize(s));
-        launched_all += launched;
-        status[0] = (int64_t)(round + 1);
-        status[1] = launched_all;
-        if (round < (uint64_t)ROUNDS_KEPT) {
-            status[8 + round] = words[0];
-            status[8 + ROUNDS_KEPT + round] = launched;
-            if (timed) status[8 + 2 * ROUNDS_KEPT + round] = now_ns() - t0;
-        }
-        if (words[0] == 0) return 0;
-        if (round + 1 >= bound) return fail("%s: no fixed point after rows * cols + 1 = %llu rounds", what, (unsigned long long)bound);
-        for (int c = 0; c < 4; ++c) count[c] = words[1 + c];
-    }
+    return run_tile_rounds(what, rows, cols, wk.rounds, status, timed, s,
+                           [&](int colour, unsigned blocks, unsigned across, unsigned tiles_y, unsigned tiles_x, const unsigned *list) {
+                               hipLaunchKernelGGL((relax_kernel<Op>), dim3(blocks), dim3(THREADS), 0, s, z, plane, rows, cols, tiles_y, tiles_x,
+                                                  colour, across, list, wk.rounds.flags, wk.rounds.head);
+                           });
 }
 
 int check_call(const char *what, const void *z, int dtype, int64_t rows, int64_t cols, const void *plane, const void *work, int64_t *status,
