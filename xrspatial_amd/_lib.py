@@ -233,6 +233,15 @@ _PROTOTYPES = {
     "xrs_cost_distance": [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int64, c_int64, c_double, c_double, c_double,
                           c_double, c_int, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int64), c_int, c_void_p],
     "xrs_cost_allocation": [c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p],
+    "xrs_stream_network_workspace_size": [c_int64, c_int64, ctypes.POINTER(ctypes.c_uint64)],
+    "xrs_stream_network": [c_void_p, c_void_p, c_int, c_int64, c_int64, c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                           ctypes.POINTER(c_int64), c_int, c_void_p],
+    "xrs_flow_watershed_workspace_size": [c_int64, c_int64, ctypes.POINTER(ctypes.c_uint64)],
+    "xrs_flow_watershed": [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int64, c_int64, c_void_p, c_void_p,
+                           ctypes.POINTER(c_int64), c_int, c_void_p],
+    "xrs_flow_length_workspace_size": [c_int64, c_int64, ctypes.POINTER(ctypes.c_uint64)],
+    "xrs_flow_length": [c_void_p, c_int64, c_int64, c_double, c_double, c_double, c_void_p, c_void_p, ctypes.POINTER(c_int64), c_int,
+                        c_void_p],
     "xrs_comm_unique_id": [c_void_p],
     "xrs_comm_init_rank": [ctypes.POINTER(c_void_p), c_void_p, c_int, c_int],
     "xrs_comm_destroy": [c_void_p],

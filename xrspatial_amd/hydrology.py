@@ -48,8 +48,48 @@ flow_accumulation, basins.  The input is a raster of such codes, staged as float
   7. more than 2^32 - 2 cells raise ValueError (the all-ones word is the null pointer).
 
 Flow paths cross chunks and shards: dask- and ShardedArray-backed rasters raise NotImplementedError.  Inside a `fuse()` scope
-the calls run eagerly.  There is no CPU fallback.  Weighted accumulation, flow length and watersheds from given pour points
-are not built.
+the calls run eagerly.  There is no CPU fallback.
+
+stream_order, stream_link, watershed, flow_length (csrc/streams.hip; stated in NumPy by tests/streams_oracle.py).
+`flow_dir` is a raster of codes as above and rules 1-3, 6 and 7 hold for it; all rasters of a call have one shape.
+
+The stream graph (stream_order, stream_link):
+  1. `flow_accum` is read in place when float32 or float64; any other numeric dtype is cast to float64 on the host;
+  2. `threshold` is a float64; NaN raises ValueError;
+  3. a stream cell is a cell with a non-NaN code and float64(flow_accum) >= threshold; a NaN accumulation is no stream cell;
+  4. the stream parent of a stream cell u is its downstream cell if that is a stream cell, else u has none: with a user's
+     accumulation a stream may end inside the raster and another begin below it;
+  5. children(v) = the stream cells whose stream parent is v; a source has none, a junction two or more;
+  6. method='shreve': the number of sources in v's upstream stream tree, v included (exact below 2^32);
+  7. method='strahler': 1 at a source; elsewhere, with m the largest order among the children, m + 1 if at least two children
+     have order m, else m;
+  8. stream_order is float64 for both methods, NaN at every cell that is no stream cell;
+  9. stream_link: head(u) = u if u has 0 or >= 2 children, else head(child);
+ 10. the link value at u is 1 + the number of heads whose linear index row * W + col is below head(u)'s: dense ids 1 .. L in
+     row-major order of the heads; a junction cell opens the link below it;
+ 11. stream_link is float64, NaN off the streams.
+The cycle test of rule 6 above runs on the stream cells, where the work is: a ring of stream cells raises ValueError, a ring
+that lies wholly off the streams touches no result and is not looked for.
+
+watershed:
+  1. a pour point is a cell that is a target of `pour_points` by `proximity`'s rule (`target_values` empty: non-zero and finite;
+     otherwise equal to one of them, compared as `proximity.target_array` says) and whose code is not NaN;
+  2. for a cell u with a non-NaN code, walk u, down(u), .. to the outlet: the result is float32(pour_points[p]) of the first
+     pour point p met, u itself included (the conversion `cost_allocation` makes), NaN if none is met;
+  3. NaN at NaN cells; nested pour points split a basin;
+  4. `pour_points`: the ten XRS_DT_* dtypes are read in place, bool and float16 widened on the host as `proximity` does.
+A cycle that holds a pour point is cut there and raises nothing; any other cycle raises.
+
+flow_length:
+  1. cx, cy, dg = cell_distances(flow_dir);
+  2. nx, ny, nd = the numbers of E/W, N/S and diagonal steps on the path from u to its outlet; the outlet's own code is no step;
+  3. the result is fl(fl(fl(nx * cx) + fl(ny * cy)) + fl(nd * dg)) in float64, the counts converted exactly, never fused;
+  4. 0.0 at outlets, NaN at NaN cells.
+This is the length by step counts: the counts are integers, so the value depends on the order of nothing; it lies within a few
+ulp of the sum taken step by step along the path and is not equal to it.
+
+Not built: upstream (longest) flow length, which is a maximum over float sums; float-weighted accumulation; HAND; snapping of
+pour points; D-infinity and multiple flow directions.
 """
 from __future__ import annotations
 
@@ -58,10 +98,11 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._launch import finish, get_stream, refuse_split_backends, resident, settle, workspace
+from ._launch import finish, get_stream, refuse_split_backends, resident, settle, widened, workspace
 from ._xr import DataArray
 from .dataset_support import supports_dataset
 from .device import DTYPE_CODE, FLOAT_SUFFIX, DeviceArray, to_device_f32
+from .proximity import target_array, widen
 from .utils import get_dataarray_resolution
 
 ACCUMULATION, BASINS = 1, 2             # XRS_FLOW_ACCUMULATION / XRS_FLOW_BASINS
@@ -72,6 +113,12 @@ MAX_CELLS = 2 ** 32 - 2
 CODES = (0, 1, 2, 4, 8, 16, 32, 64, 128)
 TILE = 64                               # XRS_FILL_TILE: the tile edge of the fill / flat relaxer
 FILL_STATUS_WORDS, FILL_STATUS_ROUNDS = 256, 80     # XRS_FILL_STATUS_WORDS / XRS_FILL_STATUS_ROUNDS
+STRAHLER, SHREVE, LINK = 1, 2, 4        # XRS_STREAM_STRAHLER / XRS_STREAM_SHREVE / XRS_STREAM_LINK
+STREAM_STATUS_WORDS = 136               # XRS_STREAM_STATUS_WORDS
+# xrs_stream_network's status words (beside [0] rounds and [1] the bits above)
+STREAM_LEVELS, STREAM_CELLS, STREAM_SOURCES, STREAM_HEADS, STREAM_HEAD_ROUNDS = 2, 3, 4, 5, 6
+STREAM_NS, STREAM_LIVE, STREAM_JOINTS, STREAM_LEVEL_ROUNDS = 8, 16, 56, 96
+POUR_POINTS = 37                        # xrs_flow_watershed's status word
 
 
 def _check_raster(data, what):
@@ -182,6 +229,14 @@ def flow_direction(agg: DataArray, name: str = 'flow_direction', resolve_flats: 
 
 
 # ------------------------------------------------------------------ flow_accumulation, basins
+def _raise_for(words):
+    """ValueError for the status bits every graph call shares (word 1; word 0: the rounds run)."""
+    if words[1] & INVALID_CODE:
+        raise ValueError("flow direction raster holds a value that is not one of the D8 codes 0, 1, 2, 4, 8, 16, 32, 64, 128")
+    if words[1] & CYCLE:
+        raise ValueError(f"flow direction raster contains a cycle (pointers still live after {words[0]} doubling rounds)")
+
+
 def flow_graph(src: DeviceArray, want: int, flags: int = 0, stream=None):
     """xrs_flow_accumulate on a resident float32 plane of codes: (accumulation or None, basins or None, status words).
     Raises ValueError for an invalid code or a cycle."""
@@ -195,10 +250,7 @@ def flow_graph(src: DeviceArray, want: int, flags: int = 0, stream=None):
                   status, flags, stream)
         settle(stream)
     words = [int(w) for w in status]
-    if words[1] & INVALID_CODE:
-        raise ValueError("flow direction raster holds a value that is not one of the D8 codes 0, 1, 2, 4, 8, 16, 32, 64, 128")
-    if words[1] & CYCLE:
-        raise ValueError(f"flow direction raster contains a cycle (pointers still live after {words[0]} doubling rounds)")
+    _raise_for(words)
     return acc, basin, words
 
 
@@ -233,3 +285,136 @@ def basins(flow_dir: DataArray, name: str = 'basins') -> DataArray:
     or whose code names a neighbour outside the raster or a NaN neighbour); NaN at NaN cells.  Arguments and errors as for
     `flow_accumulation`.  Returns a float64 DataArray."""
     return _graph_product(flow_dir, name, 'basins', BASINS)
+
+
+# ------------------------------------------------------------------ stream_order, stream_link, watershed, flow_length
+def stream_network(src: DeviceArray, accum: DeviceArray, threshold: float, want: int, flags: int = 0, stream=None):
+    """xrs_stream_network on a resident float32 plane of codes and a float32 / float64 accumulation: (Strahler or None, Shreve or
+    None, links or None, status words).  Raises ValueError for an invalid code or a ring of stream cells."""
+    rows, cols = src.shape
+    outs = [DeviceArray((rows, cols), np.float64) if want & bit else None for bit in (STRAHLER, SHREVE, LINK)]
+    status = (ctypes.c_int64 * STREAM_STATUS_WORDS)()
+    if rows * cols:
+        work = workspace("stream_network", rows, cols)
+        _lib.call("xrs_stream_network", src.ptr, accum.ptr, DTYPE_CODE[accum.dtype], rows, cols, float(threshold), want, work.ptr,
+                  *[o.ptr if o else None for o in outs], status, flags, stream)
+        settle(stream)
+    words = [int(w) for w in status]
+    _raise_for(words)
+    return (*outs, words)
+
+
+def watershed_plane(src: DeviceArray, pour: DeviceArray, values, kind, flags: int = 0, stream=None):
+    """xrs_flow_watershed on resident planes: (the float32 labels, status words).  `pour`: one of the ten dtypes of DTYPE_CODE;
+    `values`, `kind`: `proximity.target_array`'s."""
+    rows, cols = src.shape
+    out = DeviceArray((rows, cols), np.float32)
+    status = (ctypes.c_int64 * STATUS_WORDS)()
+    if rows * cols:
+        vals = DeviceArray.from_numpy(values.view(np.float64), stream=stream) if values.size else None
+        work = workspace("flow_watershed", rows, cols)
+        _lib.call("xrs_flow_watershed", src.ptr, pour.ptr, DTYPE_CODE[pour.dtype], vals.ptr if vals else None, kind, int(values.size),
+                  rows, cols, work.ptr, out.ptr, status, flags, stream)
+        settle(stream)
+    words = [int(w) for w in status]
+    _raise_for(words)
+    return out, words
+
+
+def length_plane(src: DeviceArray, cx, cy, dg, flags: int = 0, stream=None):
+    """xrs_flow_length on a resident float32 plane of codes: (the float64 lengths, status words)."""
+    rows, cols = src.shape
+    out = DeviceArray((rows, cols), np.float64)
+    status = (ctypes.c_int64 * STATUS_WORDS)()
+    if rows * cols:
+        work = workspace("flow_length", rows, cols)
+        _lib.call("xrs_flow_length", src.ptr, rows, cols, cx, cy, dg, work.ptr, out.ptr, status, flags, stream)
+        settle(stream)
+    words = [int(w) for w in status]
+    _raise_for(words)
+    return out, words
+
+
+def _check_pair(flow_dir, other, label, what):
+    for agg in (flow_dir, other):
+        refuse_split_backends(agg, what)
+    _check_raster(flow_dir.data, what)
+    _check_raster(other.data, what)
+    if tuple(flow_dir.data.shape) != tuple(other.data.shape):
+        raise ValueError(f"{what}: flow_dir and {label} differ in shape, {tuple(flow_dir.data.shape)} and {tuple(other.data.shape)}")
+
+
+def _like(flow_dir, out, name):
+    # the result has flow_dir's backend, whatever the second raster's is (as cost_distance's has `raster`'s)
+    return DataArray(finish(out, not isinstance(flow_dir.data, DeviceArray)), name=name, coords=flow_dir.coords, dims=flow_dir.dims,
+                     attrs=flow_dir.attrs)
+
+
+def _stream_product(flow_dir, flow_accum, threshold, want, name, what):
+    _check_pair(flow_dir, flow_accum, "flow_accum", what)
+    threshold = float(np.float64(threshold))
+    if np.isnan(threshold):
+        raise ValueError(f"{what}: threshold is NaN")
+    _lib.require_device()
+    stream = get_stream()
+    src = to_device_f32(flow_dir.data)
+    acc, _ = resident(flow_accum.data, stream, FLOAT_SUFFIX, np.float64)
+    *outs, _ = stream_network(src, acc, threshold, want, stream=stream)
+    return _like(flow_dir, next(o for o in outs if o is not None), name)
+
+
+def stream_order(flow_dir: DataArray, flow_accum: DataArray, threshold: float = 100, method: str = 'strahler',
+                 name: str = 'stream_order') -> DataArray:
+    """The order of every stream cell, NaN off the streams: Strahler's (1 at a source, one more where two streams of the same
+    order meet) or Shreve's (the number of sources upstream).  The rule: module docstring.
+
+    flow_dir: 2-D DataArray of D8 codes as `flow_direction` returns them; flow_accum: DataArray of the same shape, as
+    `flow_accumulation` returns it (any numeric raster will do); a stream cell is one with flow_accum >= threshold.  method:
+    'strahler' or 'shreve'.  NumPy- or DeviceArray-backed, each input staged on its own (the result's backend is flow_dir's).
+    A value that is no code, or a ring of stream cells, raises ValueError.  Returns a float64 DataArray with flow_dir's coords,
+    dims and attrs."""
+    if method not in ('strahler', 'shreve'):
+        raise ValueError(f"stream_order: method must be 'strahler' or 'shreve', got {method!r}")
+    return _stream_product(flow_dir, flow_accum, threshold, STRAHLER if method == 'strahler' else SHREVE, name, 'stream_order')
+
+
+def stream_link(flow_dir: DataArray, flow_accum: DataArray, threshold: float = 100, name: str = 'stream_link') -> DataArray:
+    """The streams cut into links (reaches between sources, junctions and stream ends): every stream cell gets the id of its
+    link, 1 .. L in row-major order of the links' upstream ends; a junction cell opens the link below it; NaN off the streams.
+    Arguments and errors as for `stream_order`.  Returns a float64 DataArray."""
+    return _stream_product(flow_dir, flow_accum, threshold, LINK, name, 'stream_link')
+
+
+def watershed(flow_dir: DataArray, pour_points: DataArray, target_values: list = [], name: str = 'watershed') -> DataArray:
+    """What drains to each pour point: every cell gets, as float32, the value `pour_points` holds at the first pour point on its
+    D8 flow path (the cell itself included); NaN where the path meets none and at NaN cells.  The rule: module docstring.
+
+    flow_dir: 2-D DataArray of D8 codes; pour_points: DataArray of the same shape whose pour points are the cells equal to one
+    of `target_values`, or with none given every non-zero finite cell.  NumPy- or DeviceArray-backed, each input staged on its
+    own (the result's backend is flow_dir's).  A value that is no code, or a cycle without a pour point, raises ValueError.
+    Returns a float32 DataArray with flow_dir's coords, dims and attrs."""
+    _check_pair(flow_dir, pour_points, "pour_points", 'watershed')
+    _lib.require_device()
+    stream = get_stream()
+    data = widened(pour_points.data, stream, DTYPE_CODE, widen('watershed'))
+    values, kind = target_array(target_values, data.dtype)              # (its TypeError comes before the upload)
+    pour, _ = resident(data, stream)
+    out, _ = watershed_plane(to_device_f32(flow_dir.data), pour, values, kind, stream=stream)
+    return _like(flow_dir, out, name)
+
+
+@supports_dataset
+def flow_length(flow_dir: DataArray, name: str = 'flow_length') -> DataArray:
+    """The downstream length of every cell's D8 flow path to its outlet, in the units of the cell size: 0 at outlets, NaN at NaN
+    cells.  It is the length by step counts -- (E/W steps) * cx + (N/S steps) * cy + (diagonal steps) * sqrt(cx^2 + cy^2), each
+    product and sum rounded once -- within a few ulp of the sum taken step by step and not equal to it (module docstring).
+
+    flow_dir: 2-D DataArray of D8 codes (or a Dataset: every variable on its own), NumPy- or DeviceArray-backed (the result's
+    backend); the cell size comes from `attrs['res']` or the coordinates, as for `flow_direction`.  A value that is no code, or a
+    cycle, raises ValueError.  Returns a float64 DataArray with flow_dir's coords, dims and attrs."""
+    refuse_split_backends(flow_dir, 'flow_length')
+    rows, cols = _check_raster(flow_dir.data, 'flow_length')
+    cx, cy, dg = cell_distances(flow_dir) if rows * cols else (1.0, 1.0, float(np.sqrt(2.0)))
+    _lib.require_device()
+    out, _ = length_plane(to_device_f32(flow_dir.data), cx, cy, dg, stream=get_stream())
+    return _like(flow_dir, out, name)
