@@ -846,6 +846,42 @@ int xrs_flow_length_workspace_size(int64_t rows, int64_t cols, uint64_t *bytes_o
 int xrs_flow_length(const float *dir_dev, int64_t rows, int64_t cols, double cellsize_x, double cellsize_y, double diag, void *work_dev,
                     double *out_dev, int64_t *status_host, int flags, void *stream);
 
+/* D-infinity flow direction and the float accumulation of shares (no reference counterpart; the rule: xrspatial_amd/hydrology.py,
+ * DESIGN.md 6q).  The neighbours counter-clockwise from east are n = 0 .. 7: E, NE, N, NW, W, SW, S, SE.  table_host: a HOST array
+ * of nine float64, the angles of the neighbours and 2 pi: 0, t, pi/2, pi - t, pi, pi + t, 3 pi/2, 2 pi - t, 2 pi with
+ * t = atan2(cellsize_y, cellsize_x); it must start at 0 and be finite and strictly increasing, and is passed on by value.
+ *   xrs_flow_direction_dinf  out_dev (float64) = the angle of steepest descent over the eight facets, in radians counter-clockwise
+ *              from east (north is row - 1), in [0, 2 pi); -1.0 where xrs_flow_direction gives 0; NaN at NaN cells.  The D8 winner
+ *              and `best` come first, as xrs_flow_direction finds them; facet o between neighbours o and o + 1 has the cardinal
+ *              neighbour c at d1 and the other cell size d2, s1 = (z - z_c) / d1, s2 = (z_c - z_diag) / d2, and is a candidate iff
+ *              s1 > 0, s2 > 0 and fl(s2 d1) < fl(s1 d2); it is taken iff fl(fl(s1 s1) + fl(s2 s2)) > the best square so far
+ *              (fl(best best) at first).  codes_dev (float32, or NULL): xrs_flow_direction's codes after xrs_flow_flats; a cell
+ *              without a winner gets the table angle of its code there.  `dtype`: XRS_DT_F32 or XRS_DT_F64.  One launch.
+ *   xrs_flow_accumulate_frac  dir_dev: with XRS_FLOW_D8 a float32 plane of codes as xrs_flow_accumulate reads it (the receiver's
+ *              share is 1.0; table_host may be NULL), with XRS_FLOW_DINF a float64 plane of angles: NaN is outside the graph, -1.0
+ *              has no receiver, an angle a in [b[o], b[o + 1]) gives neighbour o the share (b[o + 1] - a) / (b[o + 1] - b[o]) and
+ *              neighbour o + 1 the share (a - b[o]) / (b[o + 1] - b[o]), a share that is not > 0 being no edge.  weights_dev
+ *              (`weights_dtype`: XRS_DT_F32 or XRS_DT_F64; or NULL: 1.0) is a cell's own contribution w.  acc_out_dev (float64):
+ *              acc[v] = w[v], then for the donors u at E, SE, S, SW, W, NW, N, NE of v in this order
+ *              acc = fl(acc + fl(share(u -> v) * acc[u])), computed once, when all donors are final; NaN at NaN cells.  The plane is
+ *              relaxed by xrs_fill's schedule (tiles of XRS_FILL_TILE cells square, 2 x 2 colours, rounds; the call waits for the
+ *              stream once a round); "not final" is a bit of a byte plane in the workspace.
+ *   work_dev   caller-owned; xrs_flow_accumulate_frac_workspace_size writes its bytes to *bytes_out (0 for an empty raster or one
+ *              beyond XRS_FLOW_MAX_CELLS cells) and returns 0, or non-zero for a null pointer.
+ *   status_host HOST array of XRS_FRAC_STATUS_WORDS words laid out as xrs_fill's ([0] rounds, [1] tiles launched, per round k
+ *              [8 + k] cells that became final, [8 + ROUNDS + k] tiles, [8 + 2 ROUNDS + k] nanoseconds), and [2], [3] nanoseconds
+ *              of the first and the last launch; [4] XRS_FLOW_INVALID_CODE (a value that is neither; found before the rounds) |
+ *              XRS_FLOW_CYCLE (a round made no cell final and cells are left: they lie on or below a cycle) -- with either set
+ *              the call returns 0 and the plane is no product; [5] the cells left; [6] the cells of the graph.  Times only with
+ *              XRS_FRAC_TIMED. */
+enum { XRS_FLOW_D8 = 0, XRS_FLOW_DINF = 1 };
+enum { XRS_FRAC_TIMED = 1, XRS_FRAC_STATUS_WORDS = 256 };
+int xrs_flow_direction_dinf(const void *data_dev, int dtype, int64_t rows, int64_t cols, double cellsize_x, double cellsize_y, double diag,
+                            const double *table_host, const float *codes_dev, double *out_dev, void *stream);
+int xrs_flow_accumulate_frac_workspace_size(int64_t rows, int64_t cols, uint64_t *bytes_out);
+int xrs_flow_accumulate_frac(const void *dir_dev, int method, const double *table_host, const void *weights_dev, int weights_dtype,
+                             int64_t rows, int64_t cols, void *work_dev, double *acc_out_dev, int64_t *status_host, int flags, void *stream);
+
 /* multispectral.true_color (xrspatial/multispectral.py:1334-1495).
  *   xrs_nan_minmax_f32: minmax_dev[0..1] = np.nanmin / np.nanmax of a float32 plane (NaN, NaN if it holds no number);
  *   xrs_true_color_u8:  rgba[i] = { stretch(red), stretch(green), stretch(blue), alpha } with

@@ -4,7 +4,7 @@ Drop-in for the `xrspatial.*` functions on that path (same names, signatures, Da
 in/out): slope, aspect, hillshade, curvature, focal.mean / apply / focal_stats,
 convolution.convolve_2d / convolution_2d, multispectral ndvi / evi / savi (+ nbr, nbr2, ndmi),
 zonal.stats, zonal.regions, classify (binary, reclassify, equal_interval, quantile, percentiles, box_plot, std_mean,
-head_tail_breaks, maximum_breaks), natural_breaks, perlin, generate_terrain, bump, viewshed (the sweep and the ray-traced mesh variant), proximity / allocation / direction, a_star_search, cost_distance / cost_allocation / cost_backlink (least accumulated cost over a friction surface), fill / flow_direction / flow_accumulation / basins (D8 hydrology with depression fill and flat resolution), stream_order / stream_link / watershed / flow_length (Strahler and Shreve orders, stream links, watersheds from pour points, downstream flow length), local (cell_stats, combine, the frequencies, positions, rank, popularity),
+head_tail_breaks, maximum_breaks), natural_breaks, perlin, generate_terrain, bump, viewshed (the sweep and the ray-traced mesh variant), proximity / allocation / direction, a_star_search, cost_distance / cost_allocation / cost_backlink (least accumulated cost over a friction surface), fill / flow_direction / flow_accumulation / basins (D8 hydrology with depression fill and flat resolution; method='dinf' gives Tarboton's D-infinity angles and the accumulation of their float shares, weights= a float-weighted accumulation for either method), stream_order / stream_link / watershed / flow_length (Strahler and Shreve orders, stream links, watersheds from pour points, downstream flow length), local (cell_stats, combine, the frequencies, positions, rank, popularity),
 experimental.polygonize.  Python host code calling hand-written HIP kernels through the C ABI of
 libxrs_hip.so (include/xrs_hip.h); no PyTorch, CuPy, Numba or Triton involved.
 

@@ -242,6 +242,11 @@ _PROTOTYPES = {
     "xrs_flow_length_workspace_size": [c_int64, c_int64, ctypes.POINTER(ctypes.c_uint64)],
     "xrs_flow_length": [c_void_p, c_int64, c_int64, c_double, c_double, c_double, c_void_p, c_void_p, ctypes.POINTER(c_int64), c_int,
                         c_void_p],
+    "xrs_flow_direction_dinf": [c_void_p, c_int, c_int64, c_int64, c_double, c_double, c_double, ctypes.POINTER(c_double), c_void_p,
+                                c_void_p, c_void_p],
+    "xrs_flow_accumulate_frac_workspace_size": [c_int64, c_int64, ctypes.POINTER(ctypes.c_uint64)],
+    "xrs_flow_accumulate_frac": [c_void_p, c_int, ctypes.POINTER(c_double), c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p,
+                                 ctypes.POINTER(c_int64), c_int, c_void_p],
     "xrs_comm_unique_id": [c_void_p],
     "xrs_comm_init_rank": [ctypes.POINTER(c_void_p), c_void_p, c_int, c_int],
     "xrs_comm_destroy": [c_void_p],

@@ -88,8 +88,49 @@ flow_length:
 This is the length by step counts: the counts are integers, so the value depends on the order of nothing; it lies within a few
 ulp of the sum taken step by step along the path and is not equal to it.
 
-Not built: upstream (longest) flow length, which is a maximum over float sums; float-weighted accumulation; HAND; snapping of
-pour points; D-infinity and multiple flow directions.
+flow_direction(method='dinf'), flow_accumulation(method='dinf' | weights=..): Tarboton's D-infinity and the accumulation of float
+shares (csrc/flow_frac.hip; stated in NumPy by tests/dinf_oracle.py).
+
+Neighbours and the table.  The neighbours counter-clockwise from east are n = 0 .. 7: E (0, +1), NE (-1, +1), N (-1, 0),
+NW (-1, -1), W (0, -1), SW (+1, -1), S (+1, 0), SE (+1, +1); their D8 codes are 1, 128, 64, 32, 16, 8, 4, 2.  With cx, cy as
+above the host computes td = np.arctan2(cy, cx) and b[0 .. 8] = 0, td, pi/2, pi - td, pi, pi + td, 3 pi/2, 2 pi - td, 2 pi in
+float64 and passes the table by value: b[n] is neighbour n's angle, in radians counter-clockwise from east (north is
+drow = -1).  A table that does not increase strictly (extreme cell-size ratios) raises ValueError, for 'dinf' only.
+
+The direction from elevations (float64 angles in [0, 2 pi); -1.0 at a non-NaN cell with no direction; NaN at NaN cells):
+  1. D8's winner exactly as rules 1-4 of flow_direction find it: `best` (the drop) and its neighbour; with none see 4;
+  2. bestq = fl(best * best), angle = b[winner];
+  3. for each facet o = 0 .. 7, between the neighbours o and (o + 1) % 8: the cardinal neighbour is the even one, at d1 (cx for
+     E / W, cy for N / S), d2 the other cell size; s1 = (z - z_card) / d1, s2 = (z_card - z_diag) / d2, each one IEEE
+     subtraction and one division in float64; the facet has an interior candidate iff s1 > 0, s2 > 0 and
+     fl(s2 * d1) < fl(s1 * d2) (all false on NaN); its weight is q = fl(fl(s1 * s1) + fl(s2 * s2)), taken iff q > bestq
+     (strict: ties keep what is there), and then bestq = q, r = atan2(s2, s1) and the angle is b[o] + r for even o,
+     b[o + 1] - r for odd o, clamped to [b[o], b[o + 1]]; a result of b[8] becomes 0.0.  Squares that underflow or overflow
+     leave the D8 winner in place: a cell has a direction exactly where its D8 code is not 0;
+  4. a cell with no D8 winner gets -1.0; with resolve_flats=True it gets b[n] of the code that flow_direction(resolve_flats=True)
+     gives it (the same two kernels, unchanged), -1.0 if that code is still 0.
+Which candidate wins takes exact operations only; an interior angle goes through atan2, whose last bits are the library's.
+No cycle: an interior candidate has s1 > 0 and s2 > 0, so both receivers lie strictly lower; a single receiver lies strictly
+lower (its drop is > 0); a flat cell's receiver has equal height and a smaller count d.  Height never rises along a path and,
+among equal heights, d falls strictly.
+
+Decoding a direction raster for the accumulation.  A D8 code has one receiver with share 1.0, and a value that is no code is
+refused as above.  An angle a (float64; any other numeric dtype is cast to float64 on the host): NaN is outside the graph;
+-1.0 has no receiver; any other value must lie in [0, 2 pi), else ValueError (found on the device, raised before a result is
+returned).  With o such that b[o] <= a < b[o + 1], neighbour o gets share_lo = (b[o + 1] - a) / (b[o + 1] - b[o]) and neighbour
+(o + 1) % 8 gets share_hi = (a - b[o]) / (b[o + 1] - b[o]), each its own subtraction and division; a share that is not > 0 is
+no edge.  A receiver outside the raster or at a NaN cell loses the water.
+
+The accumulation (float64).  acc[v] = w[v], then for the donors u of v in the order of their positions around v -- E, SE, S,
+SW, W, NW, N, NE -- acc = fl(acc + fl(share(u -> v) * acc[u])).  w is 1.0, or with `weights` the cell's weight (float32 and
+float64 read in place, any other numeric dtype cast to float64 on the host); NaN and inf are ordinary values.  A cell is
+computed once, when all its donors are final: the result is a function of the direction raster and the weights alone,
+whatever the order of the launches, and the tests compare it bit for bit.  When a round makes no cell final and non-NaN cells
+are left, those cells lie on or below a cycle: ValueError with their number.  More than 2^32 - 2 cells raise ValueError.
+flow_accumulation(method='d8') without weights is the count of rule 4 above, by the same code as before.
+
+Not built: multiple flow directions (MFD), which need eight share planes; the wetness index; upstream (longest) flow length,
+which is a maximum over float sums; HAND; snapping of pour points.
 """
 from __future__ import annotations
 
@@ -119,6 +160,11 @@ STREAM_STATUS_WORDS = 136               # XRS_STREAM_STATUS_WORDS
 STREAM_LEVELS, STREAM_CELLS, STREAM_SOURCES, STREAM_HEADS, STREAM_HEAD_ROUNDS = 2, 3, 4, 5, 6
 STREAM_NS, STREAM_LIVE, STREAM_JOINTS, STREAM_LEVEL_ROUNDS = 8, 16, 56, 96
 POUR_POINTS = 37                        # xrs_flow_watershed's status word
+D8, DINF = 0, 1                         # XRS_FLOW_D8 / XRS_FLOW_DINF
+METHODS = {'d8': D8, 'dinf': DINF}
+FRAC_STATUS_WORDS = 256                 # XRS_FRAC_STATUS_WORDS: relax_rounds' layout and the three words below
+FRAC_BITS, FRAC_LEFT, FRAC_GRAPH = 4, 5, 6
+NEIGHBOUR_CODES = (1, 128, 64, 32, 16, 8, 4, 2)     # the D8 code of neighbour n = 0 .. 7, counter-clockwise from east
 
 
 def _check_raster(data, what):
@@ -187,6 +233,11 @@ def fill(agg: DataArray, name: str = 'fill') -> DataArray:
 
 
 # ------------------------------------------------------------------ flow_direction
+def _check_method(method, what):
+    if method not in METHODS:
+        raise ValueError(f"{what}: method must be 'd8' or 'dinf', got {method!r}")
+
+
 def resolve_flats_plane(src: DeviceArray, codes: DeviceArray, flags: int = 0, stream=None):
     """xrs_flow_flats: the codes of xrs_flow_direction for the resident plane `src`, updated in place; the status words."""
     rows, cols = src.shape
@@ -195,6 +246,47 @@ def resolve_flats_plane(src: DeviceArray, codes: DeviceArray, flags: int = 0, st
         work = workspace("flow_flats", rows, cols)
         _lib.call("xrs_flow_flats", src.ptr, DTYPE_CODE[src.dtype], rows, cols, codes.ptr, work.ptr, status, flags, stream)
     return [int(w) for w in status]
+
+
+def angle_table(cx, cy):
+    """b[0 .. 8] of the D-infinity rule: the angles of the neighbours n = 0 .. 7 (E, NE, N, NW, W, SW, S, SE), counter-clockwise
+    from east in radians, and 2 pi, as a float64 array.  ValueError where they do not increase strictly."""
+    cx, cy = np.float64(cx), np.float64(cy)
+    td, pi = np.arctan2(cy, cx), np.float64(np.pi)
+    b = np.array([0.0, td, pi / 2, pi - td, pi, pi + td, 3 * pi / 2, 2 * pi - td, 2 * pi], np.float64)
+    if not (np.isfinite(b).all() and (np.diff(b) > 0).all()):
+        raise ValueError(f"method='dinf': the cell sizes ({cx}, {cy}) leave no room between the neighbours' angles {b.tolist()}")
+    return b
+
+
+def _c_table(table):
+    return (ctypes.c_double * 9)(*[float(v) for v in table])
+
+
+def dinf_direction_plane(src: DeviceArray, cx, cy, dg, table, codes: DeviceArray = None, stream=None):
+    """xrs_flow_direction_dinf on a resident float32 / float64 plane: the float64 angles.  `codes`: the resolved D8 codes."""
+    rows, cols = src.shape
+    out = DeviceArray((rows, cols), np.float64)
+    if rows * cols:
+        _lib.call("xrs_flow_direction_dinf", src.ptr, DTYPE_CODE[src.dtype], rows, cols, cx, cy, dg, _c_table(table),
+                  codes.ptr if codes is not None else None, out.ptr, stream)
+    return out
+
+
+def _run_direction_dinf(data, cx, cy, dg, table, resolve_flats):
+    _lib.require_device()
+    stream = get_stream()
+    src, like_numpy = resident(data, stream, FLOAT_SUFFIX, np.float64)
+    rows, cols = src.shape
+    codes = None
+    if resolve_flats and rows * cols:                                    # the two D8 kernels, unchanged, then the angles
+        codes = DeviceArray((rows, cols), np.float32)
+        _lib.call("xrs_flow_direction", src.ptr, DTYPE_CODE[src.dtype], rows, cols, cx, cy, dg, codes.ptr, stream)
+        resolve_flats_plane(src, codes, stream=stream)
+    out = dinf_direction_plane(src, cx, cy, dg, table, codes, stream)
+    if rows * cols and (src is not data or resolve_flats):
+        settle(stream, like_numpy)                                       # the widened copy, the codes and the workspace go back to the pool
+    return finish(out, like_numpy)
 
 
 def _run_direction(data, cx, cy, dg, resolve_flats=False):
@@ -213,18 +305,26 @@ def _run_direction(data, cx, cy, dg, resolve_flats=False):
 
 
 @supports_dataset
-def flow_direction(agg: DataArray, name: str = 'flow_direction', resolve_flats: bool = False) -> DataArray:
+def flow_direction(agg: DataArray, name: str = 'flow_direction', resolve_flats: bool = False, method: str = 'd8') -> DataArray:
     """D8 flow direction: for every cell the ESRI code (E 1, SE 2, S 4, SW 8, W 16, NW 32, N 64, NE 128) of the neighbour with
     the steepest drop, 0 where no neighbour lies lower, NaN at NaN cells (the rule: module docstring).
+
+    method='dinf': Tarboton's D-infinity instead -- the float64 angle of steepest descent over the eight triangular facets, in
+    radians counter-clockwise from east (north is the row above) in [0, 2 pi), -1.0 where D8 gives 0, NaN at NaN cells; with
+    resolve_flats a flat cell gets the angle of the neighbour its D8 code names.  Any other method raises ValueError.
 
     agg: 2-D DataArray of elevations (or a Dataset: every variable on its own), NumPy- or DeviceArray-backed (the result's
     backend); the cell size comes from `attrs['res']` or the coordinates, as for `slope`.  resolve_flats: give every cell of a
     level area that has a drained cell the code of the neighbour one step nearer to it (on `fill(agg)` every path then ends at
-    the rim of the raster).  Returns a float32 DataArray with agg's coords, dims and attrs."""
+    the rim of the raster).  Returns a float32 DataArray (float64 for 'dinf') with agg's coords, dims and attrs."""
+    _check_method(method, 'flow_direction')
     refuse_split_backends(agg, 'flow_direction')
     rows, cols = _check_raster(agg.data, 'flow_direction')
     cx, cy, dg = cell_distances(agg) if rows * cols else (1.0, 1.0, float(np.sqrt(2.0)))
-    out = _run_direction(agg.data, cx, cy, dg, bool(resolve_flats))
+    if method == 'dinf':
+        out = _run_direction_dinf(agg.data, cx, cy, dg, angle_table(cx, cy), bool(resolve_flats))
+    else:
+        out = _run_direction(agg.data, cx, cy, dg, bool(resolve_flats))
     return DataArray(out, name=name, coords=agg.coords, dims=agg.dims, attrs=agg.attrs)
 
 
@@ -269,14 +369,71 @@ def _graph_product(flow_dir, name, what, want):
     return DataArray(out, name=name, coords=flow_dir.coords, dims=flow_dir.dims, attrs=flow_dir.attrs)
 
 
+def frac_plane(src: DeviceArray, method: int, table=None, weights: DeviceArray = None, flags: int = 0, stream=None):
+    """xrs_flow_accumulate_frac on a resident plane of D8 codes (float32, method D8) or of angles (float64, DINF, with `table`):
+    (the float64 accumulation, status words).  `weights`: a float32 / float64 plane or None.  Raises ValueError for a value that
+    is no direction and for a cycle."""
+    rows, cols = src.shape
+    out = DeviceArray((rows, cols), np.float64)
+    status = (ctypes.c_int64 * FRAC_STATUS_WORDS)()
+    if rows * cols:
+        work = workspace("flow_accumulate_frac", rows, cols)
+        _lib.call("xrs_flow_accumulate_frac", src.ptr, method, _c_table(table) if method == DINF else None,
+                  weights.ptr if weights is not None else None, DTYPE_CODE[weights.dtype] if weights is not None else 0, rows, cols,
+                  work.ptr, out.ptr, status, flags, stream)                 # (waits for the stream: the status words)
+    words = [int(w) for w in status]
+    if words[FRAC_BITS] & INVALID_CODE:
+        raise ValueError("flow direction raster holds a value that is not one of the D8 codes 0, 1, 2, 4, 8, 16, 32, 64, 128"
+                         if method == D8 else "flow direction raster holds a value that is no angle in [0, 2 pi), -1.0 or NaN")
+    if words[FRAC_BITS] & CYCLE:
+        raise ValueError(f"flow direction raster contains a cycle: {words[FRAC_LEFT]} cells lie on or below one (no cell became "
+                         f"final in round {words[0]})")
+    return out, words
+
+
+def _run_frac(flow_dir, weights, method):
+    rows, cols = (int(n) for n in flow_dir.data.shape)
+    table = None
+    if method == 'dinf':
+        cx, cy, _ = cell_distances(flow_dir) if rows * cols else (1.0, 1.0, 0.0)
+        table = angle_table(cx, cy)
+    _lib.require_device()
+    stream = get_stream()
+    if method == 'dinf':
+        src, _ = resident(flow_dir.data, stream, {np.dtype(np.float64): "f64"}, np.float64)
+    else:
+        src = to_device_f32(flow_dir.data)
+    wts = None
+    if weights is not None:
+        wts, _ = resident(weights.data, stream, FLOAT_SUFFIX, np.float64)     # staged on its own, as cost_distance's friction
+    out, _ = frac_plane(src, METHODS[method], table, wts, stream=stream)
+    return finish(out, not isinstance(flow_dir.data, DeviceArray))      # flow_dir's backend, whatever the weights' is
+
+
 @supports_dataset
-def flow_accumulation(flow_dir: DataArray, name: str = 'flow_accumulation') -> DataArray:
+def flow_accumulation(flow_dir: DataArray, name: str = 'flow_accumulation', method: str = 'd8', weights: DataArray = None) -> DataArray:
     """For every cell the number of cells whose D8 flow path reaches it, itself included; NaN at NaN cells.
 
     flow_dir: 2-D DataArray of D8 codes as `flow_direction` returns them (or a Dataset: every variable on its own), NumPy- or
-    DeviceArray-backed (the result's backend).  A value that is no code, or a cycle, raises ValueError.  Returns a float64
-    DataArray with flow_dir's coords, dims and attrs."""
-    return _graph_product(flow_dir, name, 'flow_accumulation', ACCUMULATION)
+    DeviceArray-backed (the result's backend).  A value that is no code, or a cycle, raises ValueError.
+
+    method='dinf': flow_dir holds the angles of `flow_direction(method='dinf')` instead (NaN: outside the graph; -1.0: no
+    receiver; else in [0, 2 pi), anything else raises ValueError); a cell's water is split between the two neighbours its angle
+    lies between, in proportion to the angles; the cell size comes from `attrs['res']` or the coordinates.  weights: a DataArray
+    of flow_dir's shape (any numeric dtype, read as float64; staged on its own) with every cell's own contribution in place
+    of 1.0, for both methods; NaN and inf are ordinary values.  With a method other than 'd8' or with weights the result is the
+    gather of the module docstring, a sum of floats in a fixed order.  Returns a float64 DataArray with flow_dir's coords, dims
+    and attrs."""
+    _check_method(method, 'flow_accumulation')
+    if method == 'd8' and weights is None:
+        return _graph_product(flow_dir, name, 'flow_accumulation', ACCUMULATION)
+    if weights is None:
+        refuse_split_backends(flow_dir, 'flow_accumulation')
+        _check_raster(flow_dir.data, 'flow_accumulation')
+    else:
+        _check_pair(flow_dir, weights, "weights", 'flow_accumulation')
+    out = _run_frac(flow_dir, weights, method)
+    return DataArray(out, name=name, coords=flow_dir.coords, dims=flow_dir.dims, attrs=flow_dir.attrs)
 
 
 @supports_dataset
