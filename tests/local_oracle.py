@@ -1,6 +1,7 @@
 """The rule of xrspatial_amd.local (its module docstring) as vectorised NumPy.  Test infrastructure only:
 tests/test_local_host.py holds it against the executed reference (tests/golden/local_exec.npz), tests/test_gpu_local.py holds
-the kernels against it where the reference would take minutes.
+the kernels against it where the reference would take minutes, tests/local_cases.py takes every expected value of the ABI cases
+from it (`distinct` and `combine_first_cells` were added for that table).
 
 Every function takes the planes as a list of equally shaped 2-D arrays (and `ref`, the plane of ref_var) and returns a 2-D
 array of `result_dtype`; `combine` returns (ids, key)."""
@@ -149,6 +150,23 @@ def popularity(planes, ref):
     pick = (new & (d == np.where(ok, k, 0))).argmax(axis=0)
     r = s[pick, np.arange(cells)]
     return _finish(r, bad | ~ok, "popularity", dtypes, planes[0].shape)
+
+
+def distinct(planes, ref_dtypes=(np.int64,)):
+    """u of the popularity rule: the number of distinct values of each cell in the working type (a NaN counts as 0; such a
+    cell's result is NaN anyway).  `ref_dtypes`: of the ref plane that will go with the planes (an integer one)."""
+    v = _stack(planes, working_dtype("popularity", [p.dtype for p in planes] + list(ref_dtypes)))
+    s = np.sort(np.where(np.isnan(v), 0, v) if v.dtype.kind == "f" else v, axis=0)
+    return 1 + (s[1:] != s[:-1]).sum(axis=0)
+
+
+def combine_first_cells(planes):
+    """The flat row-major index of the first cell of every class of `combine`, in id order (uint32): the list the second call
+    of xrs_local_combine returns.  The NaN cells have no class and no entry."""
+    flat = combine(planes)[0].reshape(-1)
+    good = np.flatnonzero(~np.isnan(flat))
+    _, first = np.unique(flat[good], return_index=True)
+    return good[first].astype(np.uint32)
 
 
 def combine(planes):
