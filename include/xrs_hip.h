@@ -665,6 +665,45 @@ int xrs_polygonize_scatter(const void *data_dev, int dtype, int64_t rows, int64_
                            const double *transform_host, void *points_dev, void *ring_offsets_dev, void *polygon_offsets_dev,
                            void *column_dev, void *stream);
 
+/* rasterize (no counterpart in the reference; the rule is DESIGN.md §6r): polygons burnt into a rows x cols raster (at most
+ * 2^32 - 1 cells).  The polygons come as polygonize's flat arrays: points_dev float64 [n_points][2], ring_offsets_dev int64
+ * [n_rings + 1], polygon_offsets_dev int64 [n_polygons + 1], non-decreasing, starting at 0 and ending at n_points and n_rings (the
+ * caller checks that; rings and polygons may be empty).  Pixel (row j, column i) is the square [i, i + 1] x [j, j + 1]; a cell is
+ * inside a polygon when the polygon's crossings of the cell's centre line at or left of the centre are odd in number (even-odd).
+ * (polygon, row, column) of a crossing is one 64-bit key: bits(n_polygons - 1) + bits(rows - 1) + bits(cols) <= 64, or the calls
+ * fail.  Four calls on one stream, same polygons and shape; the first two wait for the stream once each:
+ *   xrs_rasterize_census  inverse_host: NULL (the points are in pixel space) or 6 doubles a0, a1, a2, a3, t2, t5: u = a0 * dx + a1 *
+ *              dy, v = a2 * dx + a3 * dy with dx = x - t2, dy = y - t5, products and sums rounded separately.  work_dev:
+ *              xrs_rasterize_workspace_size(n_points) bytes, caller-owned.  *n_crossings (host): how often an edge crosses a
+ *              row's centre line, always even.  *flags (host): XRS_RASTERIZE_NONFINITE if a vertex is not finite, before or after
+ *              the mapping; the other calls must not follow then.  No further call but burn and gather is needed when
+ *              *n_crossings is 0.
+ *   xrs_rasterize_spans   spans_dev: xrs_rasterize_spans_workspace_size(n_crossings) bytes, caller-owned (0 when n_crossings is 0
+ *              or above XRS_RASTERIZE_MAX_CROSSINGS).  *n_spans (host): the spans [c0, c1) of one polygon in one row that are
+ *              not empty; *n_items (host): their chunks of 64 columns (aligned to multiples of 64), the work items of burn.
+ *   xrs_rasterize_burn    plane_dev: uint32 [rows][cols], cleared by the call; afterwards 0 where no polygon covers the cell, else
+ *              1 + the highest priority_dev[p] (uint32 [n_polygons], all different) among the covering polygons, or with `count`
+ *              their number.  With n_items == 0 the call only clears the plane, and spans_dev may be NULL.  Does not wait.
+ *   xrs_rasterize_gather  out_dev[c] (dtype: XRS_DT_*) = values_dev[order_dev[w - 1]] for w = plane_dev[c] > 0, else *fill_host
+ *              (one item of `dtype`); values_dev: [n_polygons] of `dtype`, order_dev: uint32, the polygon of every priority.
+ *              With `count`: the plane converted to `dtype`; values_dev, order_dev and the fill are not read.  Does not wait. */
+#define XRS_RASTERIZE_MAX_POINTS 2147483647ull
+#define XRS_RASTERIZE_MAX_CROSSINGS 2147483646ull
+enum { XRS_RASTERIZE_NONFINITE = 1 };
+int xrs_rasterize_workspace_size(uint64_t n_points, uint64_t *bytes_out);
+int xrs_rasterize_spans_workspace_size(uint64_t n_crossings, uint64_t *bytes_out);
+int xrs_rasterize_census(const double *points_dev, const int64_t *ring_offsets_dev, const int64_t *polygon_offsets_dev,
+                         uint64_t n_points, uint64_t n_rings, uint64_t n_polygons, int64_t rows, int64_t cols,
+                         const double *inverse_host, void *work_dev, uint64_t *n_crossings, int *flags, void *stream);
+int xrs_rasterize_spans(const double *points_dev, const int64_t *ring_offsets_dev, const int64_t *polygon_offsets_dev,
+                        uint64_t n_points, uint64_t n_rings, uint64_t n_polygons, int64_t rows, int64_t cols,
+                        const double *inverse_host, const void *work_dev, void *spans_dev, uint64_t n_crossings,
+                        uint64_t *n_spans, uint64_t *n_items, void *stream);
+int xrs_rasterize_burn(int64_t rows, int64_t cols, const void *spans_dev, uint64_t n_crossings, uint64_t n_polygons,
+                       uint64_t n_items, const uint32_t *priority_dev, int count, uint32_t *plane_dev, void *stream);
+int xrs_rasterize_gather(const uint32_t *plane_dev, int64_t rows, int64_t cols, const void *values_dev, const uint32_t *order_dev,
+                         int dtype, const void *fill_host, int count, void *out_dev, void *stream);
+
 /* local (xrspatial/local.py): one result per cell from the same cell of n_planes equally sized, C-contiguous planes, each read
  * in its own dtype (XRS_DT_* except XRS_DT_U64).  `planes` and `dtypes` are HOST arrays of n_planes (1 .. XRS_LOCAL_MAX_PLANES)
  * device pointers and codes; they travel in the kernel's argument block.  The rule is DESIGN.md §6f.  The working type is

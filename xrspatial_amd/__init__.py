@@ -5,7 +5,7 @@ in/out): slope, aspect, hillshade, curvature, focal.mean / apply / focal_stats,
 convolution.convolve_2d / convolution_2d, multispectral ndvi / evi / savi (+ nbr, nbr2, ndmi),
 zonal.stats, zonal.regions, classify (binary, reclassify, equal_interval, quantile, percentiles, box_plot, std_mean,
 head_tail_breaks, maximum_breaks), natural_breaks, perlin, generate_terrain, bump, viewshed (the sweep and the ray-traced mesh variant), proximity / allocation / direction, a_star_search, cost_distance / cost_allocation / cost_backlink (least accumulated cost over a friction surface), fill / flow_direction / flow_accumulation / basins (D8 hydrology with depression fill and flat resolution; method='dinf' gives Tarboton's D-infinity angles and the accumulation of their float shares, weights= a float-weighted accumulation for either method), stream_order / stream_link / watershed / flow_length (Strahler and Shreve orders, stream links, watersheds from pour points, downstream flow length), local (cell_stats, combine, the frequencies, positions, rank, popularity),
-experimental.polygonize.  Python host code calling hand-written HIP kernels through the C ABI of
+experimental.polygonize, and rasterize (polygons back into a raster; no counterpart upstream).  Python host code calling hand-written HIP kernels through the C ABI of
 libxrs_hip.so (include/xrs_hip.h); no PyTorch, CuPy, Numba or Triton involved.
 
     import xrspatial_amd as xrspatial        # numpy-backed DataArray in -> numpy-backed out
@@ -37,6 +37,7 @@ from .perlin import perlin  # noqa: F401
 from .experimental.polygonize import polygonize  # noqa: F401
 from .proximity import (allocation, direction, euclidean_distance, great_circle_distance, manhattan_distance,  # noqa: F401
                         proximity)
+from .rasterize import rasterize, transform_from_coords  # noqa: F401
 from .slope import slope  # noqa: F401
 from .terrain import generate_terrain  # noqa: F401
 from .viewshed import viewshed, viewshed_mesh  # noqa: F401

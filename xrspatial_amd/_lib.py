@@ -210,6 +210,16 @@ _PROTOTYPES = {
                              ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(c_int), c_void_p],
     "xrs_polygonize_scatter": [c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, ctypes.c_uint64, ctypes.c_uint64,
                                ctypes.c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "xrs_rasterize_workspace_size": [ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)],
+    "xrs_rasterize_spans_workspace_size": [ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)],
+    "xrs_rasterize_census": [c_void_p, c_void_p, c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, c_int64, c_int64,
+                             c_void_p, c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(c_int), c_void_p],
+    "xrs_rasterize_spans": [c_void_p, c_void_p, c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, c_int64, c_int64,
+                            c_void_p, c_void_p, c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64),
+                            ctypes.POINTER(ctypes.c_uint64), c_void_p],
+    "xrs_rasterize_burn": [c_int64, c_int64, c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, c_void_p, c_int, c_void_p,
+                           c_void_p],
+    "xrs_rasterize_gather": [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p],
     "xrs_local_cells": [c_int, ctypes.POINTER(c_void_p), ctypes.POINTER(c_int), c_int, c_void_p, c_int, c_int64, c_void_p, c_int,
                         c_void_p],
     "xrs_local_combine_workspace_bytes": [c_int64, c_int],
