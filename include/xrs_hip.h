@@ -704,6 +704,41 @@ int xrs_rasterize_burn(int64_t rows, int64_t cols, const void *spans_dev, uint64
 int xrs_rasterize_gather(const uint32_t *plane_dev, int64_t rows, int64_t cols, const void *values_dev, const uint32_t *order_dev,
                          int dtype, const void *fill_host, int count, void *out_dev, void *stream);
 
+/* contours (no counterpart in the reference; the rule is DESIGN.md §6s): the isolines of a rows x cols C-contiguous raster
+ * (`dtype`: XRS_DT_*, converted to float64; at most XRS_CONTOURS_MAX_CELLS cells) at n_levels levels by marching squares.  Node
+ * (r, c) is the centre of cell (r, c), at (c + 0.5, r + 0.5); a node is high where z > level; a quad of four nodes with a corner
+ * that is not finite draws nothing; a crossing point belongs to its edge (t = (level - z0) / (z1 - z0) from the edge's upper or
+ * left node), so the quads on either side of it get the same bits; saddles go by the centre ((zTL + zTR) + (zBR + zBL)) * 0.25.
+ * Three calls on one stream, same raster, shape and levels; the first two wait for the stream (once, and once per group of
+ * rounds), the third once:
+ *   xrs_contours_census   levels_host: n_levels finite, strictly increasing float64 (else the call fails); the raster is read
+ *              once for all of them.  work_dev: xrs_contours_workspace_size(rows, cols, n_levels) bytes, caller-owned.
+ *              *n_segments (host): the segments of all quads and levels.  No further call is needed, or allowed, when it is 0
+ *              (rows < 2, cols < 2 and n_levels == 0 among the reasons), and none is possible above XRS_CONTOURS_MAX_SEGMENTS.
+ *   xrs_contours_lines    lines_dev: xrs_contours_lines_workspace_size(n_segments) bytes, caller-owned.  *n_lines, *n_points
+ *              (host): the lines of all levels, and their points: a line of n segments has n + 1, a closed one repeats its first.
+ *              rounds (host, 2 words or NULL): the pointer-doubling rounds run to find every line's start and to rank its
+ *              segments; each is bounded by 32, beyond which the call fails.
+ *   xrs_contours_scatter  sort_dev: xrs_contours_scatter_workspace_size(n_lines) bytes, caller-owned.  transform_host: NULL or 6
+ *              doubles, x' = t0 * x + t1 * y + t2, y' = t3 * x + t4 * y + t5 with separately rounded products and sums.
+ *              points_dev: float64 [n_points][2]; line_offsets_dev: int64 [n_lines + 1], line i owns points line_offsets[i] ..
+ *              line_offsets[i + 1]; level_offsets_dev: int64 [n_levels + 1], level k owns lines level_offsets[k] ..
+ *              level_offsets[k + 1], ordered by key (an open line's first edge id, a closed line's smallest, where it begins);
+ *              closed_dev: uint8 [n_lines].  Edge ids: 2 * (r * cols + c) for (r, c)-(r, c + 1), one more for (r, c)-(r + 1, c). */
+#define XRS_CONTOURS_MAX_CELLS 2147483647ull
+#define XRS_CONTOURS_MAX_LEVELS 4194304ull
+#define XRS_CONTOURS_MAX_SEGMENTS 4294967294ull
+int xrs_contours_workspace_size(int64_t rows, int64_t cols, uint64_t n_levels, uint64_t *bytes_out);
+int xrs_contours_lines_workspace_size(uint64_t n_segments, uint64_t *bytes_out);
+int xrs_contours_scatter_workspace_size(uint64_t n_lines, uint64_t *bytes_out);
+int xrs_contours_census(const void *data_dev, int dtype, int64_t rows, int64_t cols, const double *levels_host, uint64_t n_levels,
+                        void *work_dev, uint64_t *n_segments, void *stream);
+int xrs_contours_lines(const void *data_dev, int dtype, int64_t rows, int64_t cols, uint64_t n_levels, const void *work_dev,
+                       void *lines_dev, uint64_t n_segments, uint64_t *n_lines, uint64_t *n_points, int *rounds, void *stream);
+int xrs_contours_scatter(const void *data_dev, int dtype, int64_t rows, int64_t cols, uint64_t n_levels, const void *work_dev,
+                         void *lines_dev, void *sort_dev, uint64_t n_segments, uint64_t n_lines, const double *transform_host,
+                         void *points_dev, void *line_offsets_dev, void *level_offsets_dev, void *closed_dev, void *stream);
+
 /* local (xrspatial/local.py): one result per cell from the same cell of n_planes equally sized, C-contiguous planes, each read
  * in its own dtype (XRS_DT_* except XRS_DT_U64).  `planes` and `dtypes` are HOST arrays of n_planes (1 .. XRS_LOCAL_MAX_PLANES)
  * device pointers and codes; they travel in the kernel's argument block.  The rule is DESIGN.md §6f.  The working type is

@@ -220,6 +220,15 @@ _PROTOTYPES = {
     "xrs_rasterize_burn": [c_int64, c_int64, c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, c_void_p, c_int, c_void_p,
                            c_void_p],
     "xrs_rasterize_gather": [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p],
+    "xrs_contours_workspace_size": [c_int64, c_int64, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)],
+    "xrs_contours_lines_workspace_size": [ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)],
+    "xrs_contours_scatter_workspace_size": [ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)],
+    "xrs_contours_census": [c_void_p, c_int, c_int64, c_int64, c_void_p, ctypes.c_uint64, c_void_p, ctypes.POINTER(ctypes.c_uint64),
+                            c_void_p],
+    "xrs_contours_lines": [c_void_p, c_int, c_int64, c_int64, ctypes.c_uint64, c_void_p, c_void_p, ctypes.c_uint64,
+                           ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(c_int), c_void_p],
+    "xrs_contours_scatter": [c_void_p, c_int, c_int64, c_int64, ctypes.c_uint64, c_void_p, c_void_p, c_void_p, ctypes.c_uint64,
+                             ctypes.c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "xrs_local_cells": [c_int, ctypes.POINTER(c_void_p), ctypes.POINTER(c_int), c_int, c_void_p, c_int, c_int64, c_void_p, c_int,
                         c_void_p],
     "xrs_local_combine_workspace_bytes": [c_int64, c_int],
