@@ -739,6 +739,32 @@ int xrs_contours_scatter(const void *data_dev, int dtype, int64_t rows, int64_t 
                          void *lines_dev, void *sort_dev, uint64_t n_segments, uint64_t n_lines, const double *transform_host,
                          void *points_dev, void *line_offsets_dev, void *level_offsets_dev, void *closed_dev, void *stream);
 
+/* idw (no counterpart in the reference; the rule is DESIGN.md §6t): inverse-distance interpolation of n_points scattered points
+ * (at most XRS_IDW_MAX_POINTS) onto a rows x cols raster (at most 2^32 - 1 cells) from the exact k nearest neighbours of every
+ * cell centre (column + 0.5, row + 0.5), nearest first by (d2, index) with d2 = dx * dx + dy * dy rounded step by step.  The
+ * points are sorted into square bins of bin_cells x bin_cells cells (a power of two) plus one apron ring of bins for the points
+ * outside; (ceil(cols / bin_cells) + 2) * (ceil(rows / bin_cells) + 2) is at most XRS_IDW_MAX_BINS.  Results never depend on
+ * bin_cells.  Two calls on one stream, same n_points, shape and bin_cells:
+ *   xrs_idw_bin     points_dev: float64 [n_points][2] (x, y); NULL only with n_points == 0.  inverse_host: as for
+ *              xrs_rasterize_census.  work_dev: xrs_idw_workspace_size(n_points, rows, cols, bin_cells) bytes, caller-owned.
+ *              *flags (host): XRS_IDW_NONFINITE if a coordinate is not finite, before or after the mapping; the search must
+ *              not follow then.  Waits for the stream once.
+ *   xrs_idw_search  values_dev: float64 [n_points] by point index (not read without out_dev).  k: 1 .. XRS_IDW_MAX_K; power:
+ *              1 .. 8; max_d2: the squared radius in cells, inclusive, or a negative number for none; min_points: 1 .. k, a cell
+ *              with fewer candidates gets `fill`.  out_dev: float64 (dtype XRS_DT_F64) or float32 (XRS_DT_F32) [rows][cols], or
+ *              NULL.  index_dev: int32 [k][rows][cols], the neighbours' indices, -1 where there is none, or NULL.  d2_dev:
+ *              float64 [k][rows][cols], their d2, +inf where there is none, or NULL.  At least one of the three.  Does not wait. */
+#define XRS_IDW_MAX_POINTS 2147483647ull
+#define XRS_IDW_MAX_BINS 67108864ull
+#define XRS_IDW_MAX_K 64
+enum { XRS_IDW_NONFINITE = 1 };
+int xrs_idw_workspace_size(uint64_t n_points, int64_t rows, int64_t cols, int64_t bin_cells, uint64_t *bytes_out);
+int xrs_idw_bin(const double *points_dev, uint64_t n_points, int64_t rows, int64_t cols, int64_t bin_cells,
+                const double *inverse_host, void *work_dev, int *flags, void *stream);
+int xrs_idw_search(const void *work_dev, const double *values_dev, uint64_t n_points, int64_t rows, int64_t cols,
+                   int64_t bin_cells, int k, int power, double max_d2, int min_points, double fill, int dtype, void *out_dev,
+                   int32_t *index_dev, double *d2_dev, void *stream);
+
 /* local (xrspatial/local.py): one result per cell from the same cell of n_planes equally sized, C-contiguous planes, each read
  * in its own dtype (XRS_DT_* except XRS_DT_U64).  `planes` and `dtypes` are HOST arrays of n_planes (1 .. XRS_LOCAL_MAX_PLANES)
  * device pointers and codes; they travel in the kernel's argument block.  The rule is DESIGN.md §6f.  The working type is

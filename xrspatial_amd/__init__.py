@@ -5,7 +5,7 @@ in/out): slope, aspect, hillshade, curvature, focal.mean / apply / focal_stats,
 convolution.convolve_2d / convolution_2d, multispectral ndvi / evi / savi (+ nbr, nbr2, ndmi),
 zonal.stats, zonal.regions, classify (binary, reclassify, equal_interval, quantile, percentiles, box_plot, std_mean,
 head_tail_breaks, maximum_breaks), natural_breaks, perlin, generate_terrain, bump, viewshed (the sweep and the ray-traced mesh variant), proximity / allocation / direction, a_star_search, cost_distance / cost_allocation / cost_backlink (least accumulated cost over a friction surface), fill / flow_direction / flow_accumulation / basins (D8 hydrology with depression fill and flat resolution; method='dinf' gives Tarboton's D-infinity angles and the accumulation of their float shares, weights= a float-weighted accumulation for either method), stream_order / stream_link / watershed / flow_length (Strahler and Shreve orders, stream links, watersheds from pour points, downstream flow length), local (cell_stats, combine, the frequencies, positions, rank, popularity),
-experimental.polygonize, rasterize (polygons back into a raster; no counterpart upstream), and contours (the isolines of a raster at given levels by marching squares, open and closed lines per level; no counterpart upstream).  Python host code calling hand-written HIP kernels through the C ABI of
+experimental.polygonize, rasterize (polygons back into a raster; no counterpart upstream), and contours (the isolines of a raster at given levels by marching squares, open and closed lines per level; no counterpart upstream), and idw (inverse-distance interpolation of scattered points from an exact k-nearest-neighbour search per cell, idw.neighbors for the search alone; no counterpart upstream).  Python host code calling hand-written HIP kernels through the C ABI of
 libxrs_hip.so (include/xrs_hip.h); no PyTorch, CuPy, Numba or Triton involved.
 
     import xrspatial_amd as xrspatial        # numpy-backed DataArray in -> numpy-backed out
@@ -31,6 +31,7 @@ from .sharded import ShardedArray  # noqa: F401
 from .hillshade import hillshade  # noqa: F401
 from .hydrology import basins, fill, flow_accumulation, flow_direction  # noqa: F401
 from .hydrology import flow_length, stream_link, stream_order, watershed  # noqa: F401
+from .idw import idw  # noqa: F401  (the function; idw.neighbors and idw.plan_bins hang on it)
 from .jenks import natural_breaks  # noqa: F401
 from .multispectral import arvi, evi, nbr, ndvi, savi, sipi  # noqa: F401
 from .pathfinding import a_star_search  # noqa: F401
