@@ -765,6 +765,44 @@ int xrs_idw_search(const void *work_dev, const double *values_dev, uint64_t n_po
                    int64_t bin_cells, int k, int power, double max_d2, int min_points, double fill, int dtype, void *out_dev,
                    int32_t *index_dev, double *d2_dev, void *stream);
 
+/* resample (no counterpart in the reference; the rule is DESIGN.md §6u): a src_rows x src_cols C-contiguous raster (`dtype`: any
+ * XRS_DT_* code; at most 2^32 - 1 cells and 2^31 - 1 per axis) onto a rows x cols grid (at most 2^32 - 1 cells).  All geometry
+ * is in DEVICE TABLES the caller computes, one entry per destination row and one per destination column; the calls only load,
+ * compare, multiply, add and divide, in a fixed order.  A tap table of an axis is first_dev: int32 [n] and w_dev: float64
+ * [n][taps] (1 .. XRS_RESAMPLE_MAX_TAPS): tap k of destination row (column) i is source row (column) first[i] + k with weight
+ * w[i][k].  A tap participates when its weight is not 0.  A tap that does not participate, or whose index lies outside the
+ * raster, is never read, whatever the tables hold.  A source cell is valid when it is inside the raster, not NaN and not equal to
+ * *nodata_host (one item of `dtype`, or NULL for none).  None of the calls waits.
+ *   xrs_resample_gather    out_dev[r][c] (`dtype`) = src[near_y_dev[r]][near_x_dev[c]] (int32 tables), or *fill_host (one item of
+ *              `dtype`) where either index is negative or outside the raster, or that cell is invalid.
+ *   xrs_resample_weighted  r_j = sum wx[i] * v and n_j = sum wx[i] over the participating valid taps of tap row j, ascending;
+ *              num = sum wy[j] * r_j and den = sum wy[j] * n_j over the rows with wy[j] != 0, ascending; float64, every product
+ *              and sum rounded on its own, from 0.0.  out_dev[r][c] (`out_dtype`: XRS_DT_F64 or XRS_DT_F32, rounded once) is
+ *              num / den with `divide`, else num.  near_y_dev / near_x_dev (both or neither): the cell is `fill` exactly where
+ *              xrs_resample_gather's would be; without them, where no valid tap participates.  fb_*: fallback tap tables (all
+ *              four or none); with them a cell whose window holds a participating invalid tap is computed from the fallback
+ *              tables by the same sums instead.  Up to 8 taps on both axes a workgroup shares the row sums of a tile of cells
+ *              through LDS; above, one wave walks one cell.  The result does not depend on which.
+ *   xrs_resample_select    op XRS_RESAMPLE_MIN / _MAX: the least / greatest of the participating valid cells of the window, the
+ *              first of equals in row-major order; XRS_RESAMPLE_MODE: the value with the most members (classes by ==), the
+ *              smaller value on a tie, reported as the class's first member in row-major order; taps_y * taps_x is at most
+ *              XRS_RESAMPLE_MODE_MAX_WINDOW for it.  *fill_host where no valid cell participates.  out_dev: `dtype`. */
+#define XRS_RESAMPLE_MAX_TAPS 256
+#define XRS_RESAMPLE_MODE_MAX_WINDOW 1024
+enum { XRS_RESAMPLE_MIN = 0, XRS_RESAMPLE_MAX = 1, XRS_RESAMPLE_MODE = 2 };
+int xrs_resample_gather(const void *src_dev, int dtype, int64_t src_rows, int64_t src_cols, const void *nodata_host, int64_t rows,
+                        int64_t cols, const int32_t *near_y_dev, const int32_t *near_x_dev, const void *fill_host, void *out_dev,
+                        void *stream);
+int xrs_resample_weighted(const void *src_dev, int dtype, int64_t src_rows, int64_t src_cols, const void *nodata_host, int64_t rows,
+                          int64_t cols, const int32_t *first_y_dev, const double *wy_dev, int taps_y, const int32_t *first_x_dev,
+                          const double *wx_dev, int taps_x, const int32_t *near_y_dev, const int32_t *near_x_dev,
+                          const int32_t *fb_first_y_dev, const double *fb_wy_dev, int fb_taps_y, const int32_t *fb_first_x_dev,
+                          const double *fb_wx_dev, int fb_taps_x, int divide, int out_dtype, double fill, void *out_dev,
+                          void *stream);
+int xrs_resample_select(const void *src_dev, int dtype, int64_t src_rows, int64_t src_cols, const void *nodata_host, int64_t rows,
+                        int64_t cols, const int32_t *first_y_dev, const double *wy_dev, int taps_y, const int32_t *first_x_dev,
+                        const double *wx_dev, int taps_x, int op, const void *fill_host, void *out_dev, void *stream);
+
 /* local (xrspatial/local.py): one result per cell from the same cell of n_planes equally sized, C-contiguous planes, each read
  * in its own dtype (XRS_DT_* except XRS_DT_U64).  `planes` and `dtypes` are HOST arrays of n_planes (1 .. XRS_LOCAL_MAX_PLANES)
  * device pointers and codes; they travel in the kernel's argument block.  The rule is DESIGN.md §6f.  The working type is

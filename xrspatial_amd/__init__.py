@@ -5,7 +5,7 @@ in/out): slope, aspect, hillshade, curvature, focal.mean / apply / focal_stats,
 convolution.convolve_2d / convolution_2d, multispectral ndvi / evi / savi (+ nbr, nbr2, ndmi),
 zonal.stats, zonal.regions, classify (binary, reclassify, equal_interval, quantile, percentiles, box_plot, std_mean,
 head_tail_breaks, maximum_breaks), natural_breaks, perlin, generate_terrain, bump, viewshed (the sweep and the ray-traced mesh variant), proximity / allocation / direction, a_star_search, cost_distance / cost_allocation / cost_backlink (least accumulated cost over a friction surface), fill / flow_direction / flow_accumulation / basins (D8 hydrology with depression fill and flat resolution; method='dinf' gives Tarboton's D-infinity angles and the accumulation of their float shares, weights= a float-weighted accumulation for either method), stream_order / stream_link / watershed / flow_length (Strahler and Shreve orders, stream links, watersheds from pour points, downstream flow length), local (cell_stats, combine, the frequencies, positions, rank, popularity),
-experimental.polygonize, rasterize (polygons back into a raster; no counterpart upstream), and contours (the isolines of a raster at given levels by marching squares, open and closed lines per level; no counterpart upstream), and idw (inverse-distance interpolation of scattered points from an exact k-nearest-neighbour search per cell, idw.neighbors for the search alone; no counterpart upstream).  Python host code calling hand-written HIP kernels through the C ABI of
+experimental.polygonize, rasterize (polygons back into a raster; no counterpart upstream), and contours (the isolines of a raster at given levels by marching squares, open and closed lines per level; no counterpart upstream), and idw (inverse-distance interpolation of scattered points from an exact k-nearest-neighbour search per cell, idw.neighbors for the search alone; no counterpart upstream), and resample (a raster onto another axis-aligned grid: nearest, bilinear, cubic, lanczos, average, sum, min, max, mode; no counterpart upstream).  Python host code calling hand-written HIP kernels through the C ABI of
 libxrs_hip.so (include/xrs_hip.h); no PyTorch, CuPy, Numba or Triton involved.
 
     import xrspatial_amd as xrspatial        # numpy-backed DataArray in -> numpy-backed out
@@ -40,6 +40,7 @@ from .experimental.polygonize import polygonize  # noqa: F401
 from .proximity import (allocation, direction, euclidean_distance, great_circle_distance, manhattan_distance,  # noqa: F401
                         proximity)
 from .rasterize import rasterize, transform_from_coords  # noqa: F401
+from .resample import resample  # noqa: F401  (the function; resample.tables and the table builders hang on it)
 from .slope import slope  # noqa: F401
 from .terrain import generate_terrain  # noqa: F401
 from .viewshed import viewshed, viewshed_mesh  # noqa: F401

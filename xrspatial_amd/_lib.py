@@ -233,6 +233,13 @@ _PROTOTYPES = {
     "xrs_idw_bin": [c_void_p, ctypes.c_uint64, c_int64, c_int64, c_int64, c_void_p, c_void_p, ctypes.POINTER(c_int), c_void_p],
     "xrs_idw_search": [c_void_p, c_void_p, ctypes.c_uint64, c_int64, c_int64, c_int64, c_int, c_int, c_double, c_int, c_double,
                        c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    "xrs_resample_gather": [c_void_p, c_int, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                            c_void_p],
+    "xrs_resample_weighted": [c_void_p, c_int, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int, c_void_p,
+                              c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
+                              c_double, c_void_p, c_void_p],
+    "xrs_resample_select": [c_void_p, c_int, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int, c_void_p,
+                            c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p],
     "xrs_local_cells": [c_int, ctypes.POINTER(c_void_p), ctypes.POINTER(c_int), c_int, c_void_p, c_int, c_int64, c_void_p, c_int,
                         c_void_p],
     "xrs_local_combine_workspace_bytes": [c_int64, c_int],
