@@ -514,10 +514,27 @@ def focal_stats(data, kernel, stats_funcs=FOCAL_STATS):
     return np.stack([focal_apply(data, kernel, s) for s in stats_funcs])
 
 
+def hotspot_classes(z):
+    """int8 Gi* classes of float32 z-scores.  Reference: `_calc_hotspots_numpy` (xrspatial/focal.py:881-915),
+    an @ngjit loop: Numba unifies the float32 `zscore` with the Python literals 2.33, 1.65, 1.29, 2.58, 1.96
+    to float64, so |z| is widened before it is compared (NumPy alone would compare in float32 under NEP 50,
+    which differs at |z| == float32(1.96) > 1.96: 90 instead of 95).  Rests on Numba's typing rule, not on
+    an executed reference."""
+    z = np.asarray(z)
+    with np.errstate(all="ignore"):
+        a = np.abs(z).astype(np.float64)
+        p = np.where(a >= 2.33, 0.0099, np.where(a >= 1.65, 0.0495, np.where(a >= 1.29, 0.0985, 1.0)))
+        conf = np.where((a > 2.58) & (p < 0.01), 99, np.where((a > 1.96) & (p < 0.05), 95,
+                        np.where((a > 1.65) & (p < 0.1), 90, 0)))
+        hot = np.where(z > 0, 1, np.where(z < 0, -1, 0))
+    return (hot * conf).astype(np.int8)
+
+
 def hotspots(data, kernel):
     """Getis-Ord Gi* classes.  Reference: xrspatial/focal.py:881-934 (`_calc_hotspots_numpy`,
     `_hotspots_numpy`): float32 data, convolve_2d with kernel / kernel.sum(), z-score against
-    np.nanmean / np.nanstd of the float32 raster (float32 results), thresholds as written."""
+    np.nanmean / np.nanstd of the float32 raster (float32 results), thresholds as written
+    (`hotspot_classes`)."""
     z32 = np.asarray(data).astype(F32)
     k = np.asarray(kernel)
     mean_array = convolve_2d(z32, k / k.sum())
@@ -526,12 +543,7 @@ def hotspots(data, kernel):
         raise ZeroDivisionError("Standard deviation of the input raster values is 0.")
     with np.errstate(all="ignore"):
         z = (mean_array - gmean) / gstd
-        a = np.abs(z)
-        p = np.where(a >= 2.33, 0.0099, np.where(a >= 1.65, 0.0495, np.where(a >= 1.29, 0.0985, 1.0)))
-        conf = np.where((a > 2.58) & (p < 0.01), 99, np.where((a > 1.96) & (p < 0.05), 95,
-                        np.where((a > 1.65) & (p < 0.1), 90, 0)))
-        hot = np.where(z > 0, 1, np.where(z < 0, -1, 0))
-    return (hot * conf).astype(np.int8), z
+    return hotspot_classes(z), z
 
 
 # --------------------------------------------------------------------------

@@ -180,7 +180,7 @@ def call(name, *a):
         m, o, n, gmean, gstd, _ = a
         with np.errstate(all="ignore"):
             z = (_arr(m, n, np.float32) - np.float32(gmean)) / np.float32(gstd)
-            az = np.abs(z)
+            az = np.abs(z).astype(np.float64)                        # the thresholds are float64 values, as in classify() of hotspots.hip
             p = np.where(az >= 2.33, 0.0099, np.where(az >= 1.65, 0.0495, np.where(az >= 1.29, 0.0985, 1.0)))
             conf = np.where((az > 2.58) & (p < 0.01), 99, np.where((az > 1.96) & (p < 0.05), 95, np.where((az > 1.65) & (p < 0.1), 90, 0)))
             _arr(o, n, np.int8)[...] = (np.where(z > 0, 1, np.where(z < 0, -1, 0)) * conf).astype(np.int8)

@@ -5,7 +5,8 @@
 // {0, +-90, +-95, +-99}.  The convolution is xrs_convolve2d_f32; here:
 //   xrs_nan_moments_f32   ONE streaming pass over shifted values (count, sum, sum of squares in float64):
 //                         wave64 DPP reductions, one atomic per wave;
-//   xrs_hotspots_classify_f32   z in float32 exactly as the reference forms it, int8 out (4 B in + 1 B out per cell).
+//   xrs_hotspots_classify_f32   z in float32 exactly as the reference forms it, compared with the thresholds as float64
+//                         values (classify() below), int8 out (4 B in + 1 B out per cell).
 #include "xrs_common.h"
 
 #include "wave_reduce.h"
@@ -114,17 +115,30 @@ __global__ void moments_final_kernel(Moments *m) {
     }
 }
 
+// The reference's Numba loop compares the float32 z-score with the Python literals 2.33, 1.65, ... in FLOAT64 (Numba unifies
+// float32 with a float64 constant to float64).  For a float32 `a` and a double `t`,  (double)a >= t  is  a >= the smallest
+// float32 not below t,  and  (double)a > t  is  a > the largest float32 not above t:  so the ladder stays in float32 with
+// these constants.  Rounding t to float32 instead differs at one magnitude, a == 1.96f (which lies above 1.96: 95, not 90).
+constexpr bool ceil32_of(float c, double t, float ulp) { return (double)c >= t && (double)(c - ulp) < t; }
+constexpr bool floor32_of(float c, double t, float ulp) { return (double)c <= t && (double)(c + ulp) > t; }
+constexpr float GE_1_29 = 0x1.4a3d72p+0f, GE_1_65 = 0x1.a66668p+0f, GE_2_33 = 0x1.2a3d72p+1f;
+constexpr float GT_1_65 = 0x1.a66666p+0f, GT_1_96 = 0x1.f5c28ep+0f, GT_2_58 = 0x1.4a3d70p+1f;
+static_assert(ceil32_of(GE_1_29, 1.29, 0x1p-23f) && ceil32_of(GE_1_65, 1.65, 0x1p-23f) && ceil32_of(GE_2_33, 2.33, 0x1p-22f),
+              "not the smallest float32 at or above the reference's thresholds");
+static_assert(floor32_of(GT_1_65, 1.65, 0x1p-23f) && floor32_of(GT_1_96, 1.96, 0x1p-23f) && floor32_of(GT_2_58, 2.58, 0x1p-22f),
+              "not the largest float32 at or below the reference's thresholds");
+
 __device__ __forceinline__ signed char classify(float z) {
     // focal.py:889-909
     const float a = fabsf(z);
     float p = 1.0f;
-    if (a >= 2.33f) p = 0.0099f;
-    else if (a >= 1.65f) p = 0.0495f;
-    else if (a >= 1.29f) p = 0.0985f;
+    if (a >= GE_2_33) p = 0.0099f;
+    else if (a >= GE_1_65) p = 0.0495f;
+    else if (a >= GE_1_29) p = 0.0985f;
     int conf = 0;
-    if (a > 2.58f && p < 0.01f) conf = 99;
-    else if (a > 1.96f && p < 0.05f) conf = 95;
-    else if (a > 1.65f && p < 0.1f) conf = 90;
+    if (a > GT_2_58 && p < 0.01f) conf = 99;
+    else if (a > GT_1_96 && p < 0.05f) conf = 95;
+    else if (a > GT_1_65 && p < 0.1f) conf = 90;
     const int hot = z > 0.0f ? 1 : (z < 0.0f ? -1 : 0);
     return (signed char)(hot * conf);
 }
